@@ -9,6 +9,14 @@ all-gather of the decoded tiles.  Default workload = BASELINE.json configs[1]: o
     python bench.py --gpus N --steps K --warmup W            (N > 1: under torch.distributed.run, or
                                                              bench.py starts the N ranks itself)
     python bench.py --config 2|3|4                           (BASELINE.json configs[2] / [3] / [4])
+    python bench.py ... --full                               (the diagnostics beside the headline figure)
+    python bench.py ... --dump-outputs DIR                   (the last timed step's outputs as DIR/<name>.npy)
+
+A plain run does only what the headline figure needs: set-up, W warm-up steps, K timed steps, the optional
+output dump, the result line.  --full adds, after the timed steps, the legs that take runs of their own: the
+event-timed denoise / decode breakdown with the MFMA roofline and the PMC traffic, the per kernel-class split
+(--no-profile skips it), the configs[4] prompt-loop and real-LQ end-to-end probes (--no-stage3-probe) and the
+CPU baseline (--no-cpu-baseline); without --full those fields of the line are null.
 
 Workloads (BASELINE.json configs; --config picks the preset):
 * configs[1] (default): one 512^2 tile per GPU per bench step;
@@ -19,7 +27,7 @@ Workloads (BASELINE.json configs; --config picks the preset):
   (--split overlap: the val_patches rule, 81 tiles per image, device overlap-blend stitch);
 * configs[4]: the stage-3 prompt loop (TESTR + CLIP-H re-prompt after every step).
 
-Rank 0 prints ONE JSON line (metric, value, roofline, cpu_baseline, ...).
+Rank 0 prints ONE JSON line (metric, value, unit, ms_per_step, ...; with --full also roofline, cpu_baseline, ...).
 """
 from __future__ import annotations
 
@@ -64,12 +72,17 @@ def parse():
     ap.add_argument("--sampling-steps", type=int, default=50)
     ap.add_argument("--vae", default=BENCH_VAE, choices=["hip", "bf16", "fp32"],
                     help="VAE decoder: HIP split-precision, or stock torch at bf16 / fp32")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-profile", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the timed steps also run the diagnostics: event-timed breakdown + roofline, kernel-class "
+                         "split, stage-3 and real-LQ probes, CPU baseline (each has its own --no-... switch)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write what the last timed step returned (the restored image(s) of rank 0) as DIR/<name>.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="(--full) skip the CPU baseline")
+    ap.add_argument("--no-profile", action="store_true", help="(--full) skip the kernel-class split")
     ap.add_argument("--eager", action="store_true", help="disable hipGraph replay (debug)")
     ap.add_argument("--profile-only", action="store_true", help="(rocprof) one eager profiled restoration")
     ap.add_argument("--no-stage3-probe", action="store_true",
-                    help="skip the short configs[4] prompt-loop timing the default run reports beside the line")
+                    help="(--full) skip the short configs[4] prompt-loop and real-LQ probes")
     ap.add_argument("--stage3", action="store_true",
                     help="configs[4] prompt loop: val_sample with TESTR + CLIP-H re-prompting after every step")
     ap.add_argument("--images", type=int, default=0,
@@ -86,6 +99,8 @@ def parse():
     ap.add_argument("--config", type=int, default=1, choices=[1, 2, 3, 4],
                     help="BASELINE.json configs[k] preset (overrides --tiles/--batch/--stitch/--images/--stage3)")
     a = ap.parse_args()
+    if a.steps < 1:
+        ap.error("--steps must be at least 1")
     if a.config == 2:
         a.tiles, a.batch, a.stitch = 256, 64, True
     elif a.config == 3:
@@ -342,6 +357,29 @@ def e2e_probe(model, sampler, dev, steps=50):
                     "HIP VAE encode, CLIP-H text tower, 50-step hipGraph sampler, HIP VAE decode, merge"}
 
 
+DUMP_BUDGET = 48 << 20  # bytes over all dumped arrays: the files stay below 64 MB (decimal) with their headers
+DUMP_SEED = 1234
+
+
+def dump_outputs(path, arrays):
+    """Writes {name: tensor} as path/<name>.npy in float32 (float64 stays float64).  When the arrays exceed
+    DUMP_BUDGET in all, each one larger than its share is replaced by a fixed sample of its flattened elements
+    (sorted indices drawn once from numpy's default_rng(DUMP_SEED) over the array's size, the same for every run
+    of the same arguments)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    arrays = {k: (v if v.dtype == torch.float64 else v.float()) for k, v in arrays.items()}
+    total = sum(v.numel() * v.element_size() for v in arrays.values())
+    share = DUMP_BUDGET // max(1, len(arrays))
+    for name, v in arrays.items():
+        if total > DUMP_BUDGET and v.numel() * v.element_size() > share:
+            n = share // v.element_size()
+            idx = np.sort(np.random.default_rng(DUMP_SEED).integers(0, v.numel(), size=n))
+            v = v.reshape(-1)[torch.from_numpy(idx).to(v.device)]
+            log(f"dump: {name} sampled to {n} of its elements")
+        np.save(os.path.join(path, name + ".npy"), v.detach().cpu().numpy())
+
+
 def workload_name(args, T, B, S):
     if args.images:
         from tair_amd.tiling import image_tile_grid
@@ -503,8 +541,10 @@ def main():
     tdist.barrier(dev)
     torch.cuda.synchronize(dev)
     t_start = time.perf_counter()
+    out = None
     for k in range(args.steps):
-        one()
+        del out  # (the previous step's result is released before the next, as when it was not kept)
+        out = one()
         if T > B or B >= 16 or args.stage3:  # long steps: keep the run visibly alive (progress on stderr)
             log(f"step {k + 1}/{args.steps} issued")
     torch.cuda.synchronize(dev)
@@ -514,64 +554,75 @@ def main():
     elapsed = tdist.max_over_ranks(elapsed, dev)
     ms_per_step = 1000.0 * elapsed / args.steps
     value = out_mpix * args.steps / elapsed  # unique output pixels of the job
-    # per-restoration breakdown from a separate, event-timed pass (events between micro-batches
-    # synchronise the host, so this pass is not the timed region)
-    one(timed=True)
-    denoise_ms, decode_ms = timing["denoise_ms"], timing["decode_ms"]
+    if args.dump_outputs and rank == 0:  # what the last timed step returned, outside the timed region
+        outs = list(out) if isinstance(out, (list, tuple)) else [out]
+        dump_outputs(args.dump_outputs, {"image" if len(outs) == 1 else f"image_{k}": o for k, o in enumerate(outs)})
 
-    fwd_flops = model.flops_per_forward(1) * T  # per denoise step over this rank's tiles
-    e2e = fwd_flops * S / (denoise_ms / 1000.0) / 1e12
+    # everything below the headline figure takes runs of its own: only with --full
+    breakdown = roof = classes = stage3 = e2e = cpu = None
+    if args.full:
+        # per-restoration breakdown from a separate, event-timed pass (events between micro-batches
+        # synchronise the host, so this pass is not the timed region)
+        one(timed=True)
+        denoise_ms, decode_ms = timing["denoise_ms"], timing["decode_ms"]
+        breakdown = {"denoise_all_tiles": round(denoise_ms, 3), "vae_decode": round(decode_ms, 3),
+                     "denoise_includes": ("HIP steps + TESTR + CLIP re-prompt per step" if args.stage3
+                                          else "HIP steps"),
+                     "per_denoise_step_per_micro_batch": round(denoise_ms / S / len(mbs), 4)}
 
-    # Roofline of the dominant "kernel": the hipGraph-replayed denoise step (one graph launch = one
-    # ControlNet + UNet forward + p_sample; ~85% of its FLOPs are gemm_tile_kernel launches).  achieved =
-    # algorithmic FLOPs of the step (model.flops_per_forward, the dry-run count of every MFMA launch)
-    # / the step's duration from HIP events on the launch stream over the timed region.
-    # the stage-3 loop's denoise step is the same step graph (its prompt-path kernels are not HIP kernels)
-    traffic, traffic_note = step_traffic(pmc_summary_path(B, args.fp8))
-    roof = {"bound": "mfma", "achieved": round(e2e, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
-            "frac": round(e2e / PEAK_BF16_TFLOPS, 4), "traffic": traffic,
-            "traffic_unit": "bytes beyond L2 per denoise step (= per launch of the step graph), all tair kernels: "
-                            "rocprofv3 PMC passes FETCH_SIZE x2 + WRITE_SIZE of this code "
-                            f"(scripts/gpu_profile.sh -> {os.path.relpath(pmc_summary_path(B, args.fp8), ROOT)}; PMC "
-                            "needs passes of its own, so they are not collected inside the timed run); null when "
-                            "this workload has no committed summary",
-            "traffic_note": traffic_note,
-            "kernel": "denoise-step hipGraph (ControlNet+UNet MFMA kernels + fused p_sample), per launch",
-            "flops_per_launch": fwd_flops / len(mbs), "avg_launch_ms": round(denoise_ms / S / len(mbs), 4),
-            "hbm_gbps_at_traffic": round(traffic / (denoise_ms / S / 1000.0) / 1e9, 1) if traffic else None}
-    classes = None
-    if not args.no_profile:
-        # diagnostic split by kernel class from one eager step with an event pair around every
-        # launch; the event records add ~1.6x per launch vs the graph (rocprof), so only ratios count
-        i, j = mbs[0]
-        classes = kernel_roofline(model, sampler, x_T[i:j], noise[:, i:j], mb_cond(i, j), dev)
+        fwd_flops = model.flops_per_forward(1) * T  # per denoise step over this rank's tiles
+        e2e = fwd_flops * S / (denoise_ms / 1000.0) / 1e12
 
-    stage3 = None
-    if rank == 0 and world == 1 and not args.stage3 and not args.images and not args.no_stage3_probe:
-        # configs[4]'s prompt loop at B = 1 for a few steps: graph-replayed HIP step, TESTR (full size), one
-        # host sync, CLIP-H re-encode of the recognised-text prompt, cross-attention K/V re-projection
-        try:
-            stage3 = stage3_probe(model, sampler, x_T[:1], noise[:, :1], mb_cond(0, 1), dev)
-        except Exception as e:  # diagnostic only: never hides the GPU result
-            stage3 = {"error": str(e)[:200]}
+        # Roofline of the dominant "kernel": the hipGraph-replayed denoise step (one graph launch = one
+        # ControlNet + UNet forward + p_sample; ~85% of its FLOPs are gemm_tile_kernel launches).  achieved =
+        # algorithmic FLOPs of the step (model.flops_per_forward, the dry-run count of every MFMA launch)
+        # / the step's duration from HIP events on the launch stream over the timed region.
+        # the stage-3 loop's denoise step is the same step graph (its prompt-path kernels are not HIP kernels)
+        traffic, traffic_note = step_traffic(pmc_summary_path(B, args.fp8))
+        roof = {"bound": "mfma", "achieved": round(e2e, 2), "peak": PEAK_BF16_TFLOPS, "unit": "TFLOP/s",
+                "frac": round(e2e / PEAK_BF16_TFLOPS, 4), "traffic": traffic,
+                "traffic_unit": "bytes beyond L2 per denoise step (= per launch of the step graph), all tair kernels: "
+                                "rocprofv3 PMC passes FETCH_SIZE x2 + WRITE_SIZE of this code "
+                                f"(scripts/gpu_profile.sh -> {os.path.relpath(pmc_summary_path(B, args.fp8), ROOT)}; PMC "
+                                "needs passes of its own, so they are not collected inside the timed run); null when "
+                                "this workload has no committed summary",
+                "traffic_note": traffic_note,
+                "kernel": "denoise-step hipGraph (ControlNet+UNet MFMA kernels + fused p_sample), per launch",
+                "flops_per_launch": fwd_flops / len(mbs), "avg_launch_ms": round(denoise_ms / S / len(mbs), 4),
+                "hbm_gbps_at_traffic": round(traffic / (denoise_ms / S / 1000.0) / 1e9, 1) if traffic else None}
+        classes = None
+        if not args.no_profile:
+            # diagnostic split by kernel class from one eager step with an event pair around every
+            # launch; the event records add ~1.6x per launch vs the graph (rocprof), so only ratios count
+            i, j = mbs[0]
+            classes = kernel_roofline(model, sampler, x_T[i:j], noise[:, i:j], mb_cond(i, j), dev)
 
-    e2e = None
-    if rank == 0 and world == 1 and not args.stage3 and not args.images and not args.no_stage3_probe and B <= 4:
-        try:
-            m4 = ControlLDM(max_batch=4, device=dev)
-            m4.load_state_dict(sd)
-            m4.vae.load_state_dict(vae_sd)
-            e2e = e2e_probe(m4, sampler, dev, S)
-            m4.close()
-        except Exception as e:  # diagnostic only: never hides the GPU result
-            e2e = {"error": str(e)[:300]}
+        stage3 = None
+        if rank == 0 and world == 1 and not args.stage3 and not args.images and not args.no_stage3_probe:
+            # configs[4]'s prompt loop at B = 1 for a few steps: graph-replayed HIP step, TESTR (full size), one
+            # host sync, CLIP-H re-encode of the recognised-text prompt, cross-attention K/V re-projection
+            try:
+                stage3 = stage3_probe(model, sampler, x_T[:1], noise[:, :1], mb_cond(0, 1), dev)
+            except Exception as e:  # diagnostic only: never hides the GPU result
+                stage3 = {"error": str(e)[:200]}
 
-    cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
-        try:
-            cpu = cpu_baseline(sd, vae_sd)
-        except Exception as e:  # the CPU leg must never hide the GPU result
-            cpu = dict(value=None, unit="Mpix/s", cores=None, kind="port", sample=f"failed: {e}")
+        e2e = None
+        if rank == 0 and world == 1 and not args.stage3 and not args.images and not args.no_stage3_probe and B <= 4:
+            try:
+                m4 = ControlLDM(max_batch=4, device=dev)
+                m4.load_state_dict(sd)
+                m4.vae.load_state_dict(vae_sd)
+                e2e = e2e_probe(m4, sampler, dev, S)
+                m4.close()
+            except Exception as e:  # diagnostic only: never hides the GPU result
+                e2e = {"error": str(e)[:300]}
+
+        cpu = None
+        if rank == 0 and world == 1 and not args.no_cpu_baseline:
+            try:
+                cpu = cpu_baseline(sd, vae_sd)
+            except Exception as e:  # the CPU leg must never hide the GPU result
+                cpu = dict(value=None, unit="Mpix/s", cores=None, kind="port", sample=f"failed: {e}")
     del sd
 
     if peer.get("st") is not None:
@@ -589,10 +640,7 @@ def main():
                        "parallelism": (f"dp{world} (tile-sharded; stitch reads every rank's IPC-exported tile block)"
                                        if args.images else f"dp{world} (tile-sharded replicas; RCCL all-gather of "
                                        "decoded tiles)")},
-            "breakdown_ms": {"denoise_all_tiles": round(denoise_ms, 3), "vae_decode": round(decode_ms, 3),
-                             "denoise_includes": ("HIP steps + TESTR + CLIP re-prompt per step" if args.stage3
-                                                  else "HIP steps"),
-                             "per_denoise_step_per_micro_batch": round(denoise_ms / S / len(mbs), 4)},
+            "breakdown_ms": breakdown,
             "roofline": roof,
             "kernel_classes": classes,
             "stage3_prompt_loop": stage3,

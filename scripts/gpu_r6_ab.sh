@@ -14,7 +14,8 @@ import json, sys
 for line in open(sys.argv[3]):
     if line.startswith("{"):
         d = json.loads(line)
-        print(sys.argv[1], sys.argv[2], d["value"], d["ms_per_step"], d["roofline"]["frac"], flush=True)
+        # the roofline fraction exists only when BENCH_ARGS carries --full (a plain run times the headline alone)
+        print(sys.argv[1], sys.argv[2], d["value"], d["ms_per_step"], (d.get("roofline") or {}).get("frac"), flush=True)
 PY
   done
 done

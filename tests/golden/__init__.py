@@ -3,6 +3,10 @@
 `hq_sa_922529_crop_0.jpg` is one of the reference's demo HQ crops
 (`assets/demo_imgs/hq/sa_922529_crop_0.jpg`, 512x512 RGB), kept as data: the 50-step image gates
 take PSNR against this structured image instead of uniform noise.
+
+`val_terediff_baidu_crop.yaml` is the reference's validation settings file (`configs/val/`), unchanged;
+`bpe_simple_vocab_head.txt.gz` holds the first 48,895 lines of the reference's CLIP BPE merge table
+(`bpe_simple_vocab_16e6.txt.gz`): the header and every merge the tokenizers read (tests/test_clip_cpu.py).
 """
 import os
 

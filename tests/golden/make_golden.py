@@ -138,6 +138,44 @@ def make(name: str, spec: dict) -> dict:
     return out
 
 
+MAX_FILE = 1 << 20  # no committed file above 1 MiB: a larger fixture continues in <name>_part<k>.npz
+
+
+def _parts(name: str) -> list:
+    import glob
+    return sorted(glob.glob(os.path.join(HERE, f"{name}_part[0-9].npz")))
+
+
+def save_golden(name: str, arrs: dict) -> None:
+    """<name>.npz, continued in <name>_part1.npz, ... so that no file exceeds MAX_FILE: arrays in sorted key
+    order, a new file whenever the next array's compressed size would take the current one past 7/8 of it."""
+    import io
+    for p in _parts(name):
+        os.remove(p)
+    files, size = [{}], 0
+    for k in sorted(arrs):
+        buf = io.BytesIO()
+        np.savez_compressed(buf, **{k: arrs[k]})
+        n = buf.getbuffer().nbytes
+        if files[-1] and size + n > MAX_FILE * 7 // 8:
+            files.append({})
+            size = 0
+        files[-1][k] = arrs[k]
+        size += n
+    for i, part in enumerate(files):
+        path = os.path.join(HERE, f"{name}.npz" if i == 0 else f"{name}_part{i}.npz")
+        np.savez_compressed(path, **part)
+        assert os.path.getsize(path) <= MAX_FILE, path
+
+
+def load_golden(name: str) -> dict:
+    """The fixture's arrays: <name>.npz and, where the fixture is split, its <name>_part<k>.npz files."""
+    g = dict(np.load(os.path.join(HERE, f"{name}.npz")))
+    for p in _parts(name):
+        g.update(np.load(p))
+    return g
+
+
 def main(names=None):
     meta = {"generator": "tests/golden/make_golden.py", "weight_seed": WEIGHT_SEED, "norm_seed": NORM_SEED,
             "torch": torch.__version__, "configs": {}}
@@ -145,7 +183,7 @@ def main(names=None):
         if names and name not in names:
             continue
         arrs = make(name, spec)
-        np.savez_compressed(os.path.join(HERE, f"{name}.npz"), **arrs)
+        save_golden(name, arrs)
         meta["configs"][name] = {k: (list(v) if isinstance(v, tuple) else v) for k, v in spec.items()}
     path = os.path.join(HERE, "golden.json")
     if names and os.path.exists(path):

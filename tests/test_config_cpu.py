@@ -8,7 +8,7 @@ from tair_amd.cldm import _cfg_from_dict
 from tair_amd.weights import manifest
 
 HERE = os.path.dirname(os.path.abspath(__file__))
-REF_YAML = "/root/reference/configs/val/val_terediff_baidu_crop.yaml"
+REF_YAML = os.path.join(HERE, "golden", "val_terediff_baidu_crop.yaml")  # the reference's validation settings (data)
 
 
 def test_small_config_builds_matching_manifest():
@@ -34,7 +34,6 @@ def test_rejects_unknown_target_and_mismatched_controlnet(tmp_path):
         config.cldm_params(cfg)
 
 
-@pytest.mark.skipif(not os.path.exists(REF_YAML), reason="reference tree not present")
 def test_reference_val_config_gives_default_architecture():
     cfg = config.load_config(REF_YAML)
     p = config.cldm_params(cfg)

@@ -283,5 +283,35 @@ def test_bench_config_presets():
         a = bench.parse()
         assert (a.job_tiles, a.batch) == (512, 64)
         assert "fixed job" in bench.workload_name(a, 64, 64, 50)
+        assert not a.full and a.dump_outputs is None  # a plain run: the headline figure alone
+        sys.argv = ["bench.py", "--gpus", "1", "--steps", "7", "--warmup", "2", "--full", "--dump-outputs", "d"]
+        a = bench.parse()
+        assert (a.steps, a.warmup, a.full, a.dump_outputs) == (7, 2, True, "d")
     finally:
         sys.argv = argv
+
+
+def test_bench_dump_outputs_whole_and_sampled(tmp_path, monkeypatch):
+    """--dump-outputs: float32 .npy per output; arrays over the byte budget become a fixed sample, the same
+    elements on every call."""
+    import sys
+    import numpy as np
+    import torch
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    sys.path.insert(0, root)
+    import bench
+    img = torch.arange(3 * 16 * 16, dtype=torch.bfloat16).reshape(1, 3, 16, 16)
+    bench.dump_outputs(str(tmp_path / "a"), {"image": img})
+    got = np.load(tmp_path / "a" / "image.npy")
+    assert got.dtype == np.float32 and got.shape == (1, 3, 16, 16)
+    assert np.array_equal(got, img.float().numpy())
+    monkeypatch.setattr(bench, "DUMP_BUDGET", 1024)  # 256 floats in all: the 768-element image is sampled
+    small = torch.ones(4, dtype=torch.float64)
+    for d in ("b", "c"):
+        bench.dump_outputs(str(tmp_path / d), {"image_0": img, "image_1": small})
+    b, c = np.load(tmp_path / "b" / "image_0.npy"), np.load(tmp_path / "c" / "image_0.npy")
+    assert b.shape == (128,) and np.array_equal(b, c)
+    assert np.all(np.diff(b) >= 0) and set(b.tolist()) <= set(img.float().flatten().tolist())
+    assert np.load(tmp_path / "b" / "image_1.npy").dtype == np.float64  # under its share: whole
+    total = sum(os.path.getsize(tmp_path / "b" / f) for f in os.listdir(tmp_path / "b"))
+    assert total <= 1024 + 2 * 128  # the data within the budget (+ the .npy headers)

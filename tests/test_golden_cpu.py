@@ -19,7 +19,7 @@ TOL = 1e-5
 
 
 def load(name):
-    return dict(np.load(os.path.join(HERE, f"{name}.npz")))
+    return mg.load_golden(name)
 
 
 def rel(a, b):

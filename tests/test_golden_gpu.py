@@ -40,7 +40,7 @@ def gate(tag, value, tol):
 def _model(name):
     from tair_amd.cldm import ControlLDM
     spec = mg.CONFIGS[name]
-    g = dict(np.load(os.path.join(HERE, f"{name}.npz")))
+    g = mg.load_golden(name)
     m = ControlLDM(mg.unet_cfg_dict(spec["cfg"]), max_batch=spec["batch"], latent_hw=(spec["latent"],) * 2,
                    with_vae=spec["vae"])
     sd = mg.weights(spec["cfg"])

@@ -160,15 +160,12 @@ def test_fresh_checkout_builds_library_on_first_use(tmp_path):
     import subprocess
     import sys
     dst = tmp_path / "repo"
-    git_files = subprocess.run(["git", "ls-files"], cwd=ROOT, capture_output=True, text=True, check=True).stdout.split()
-    for f in git_files:
-        if f.startswith(("tair_amd/", "include/")) and os.path.exists(os.path.join(ROOT, f)):
-            (dst / f).parent.mkdir(parents=True, exist_ok=True)
-            shutil.copy2(os.path.join(ROOT, f), dst / f)
-    for f in ("tair_amd/csrc",):  # untracked-but-present sources of this working tree (new files)
-        for name in os.listdir(os.path.join(ROOT, f)):
-            if not (dst / f / name).exists():
-                shutil.copy2(os.path.join(ROOT, f, name), dst / f / name)
+    # the sources as a clone carries them: everything under tair_amd/ and include/ but the build's own products
+    # (the tree is walked, not asked of git: an exported or foreign-owned checkout has no usable .git)
+    products = shutil.ignore_patterns("*.so", "*.srchash", "*.tmp", "*.o", ".build.lock", "__pycache__", "*.pyc")
+    for d in ("tair_amd", "include"):
+        shutil.copytree(os.path.join(ROOT, d), dst / d, ignore=products)
+    assert (dst / "tair_amd" / "csrc").is_dir() and (dst / "include" / "tair_cldm.h").exists()
     assert not (dst / "tair_amd" / "libtair_cldm.so").exists()
     code = ("import sys; sys.path.insert(0, %r); from tair_amd import _lib; L = _lib.lib(); "
             "print(L.tair_version().decode())" % str(dst))
