@@ -112,6 +112,25 @@ typedef struct {
 /* Uploads the per-restoration invariants: time-embedding tables for every step (one batched GEMM),
  * cross-attention K/V of c_txt, hint/x_T layout conversion, noise re-layout; resets step counter. */
 int tair_sampler_prepare(tair_cldm* h, const tair_sampler_io* io, tair_stream_t stream);
+
+/* Classifier-free guidance (spaced_sampler.py:149-167, sampler.py:31-38): the negative-prompt half of a
+ * guided restoration.  Each step then runs the network once at batch 2B (rows [0,B) cond, [B,2B) uncond)
+ * and the fused update forms v = v_uncond + scales[i] * (v_cond - v_uncond) before p_sample. */
+typedef struct {
+  const float* c_txt;    /* [c_txt_batch, 77, ctx] negative-prompt context */
+  int c_txt_batch;       /* 1 or B, independent of the cond's */
+  const float* c_img;    /* [B,4,h,w], or NULL = the cond's c_img */
+  const float* scales;   /* HOST [n_steps]: guidance scale at loop index i */
+} tair_guidance_io;
+/* tair_sampler_prepare with guidance.  g == NULL is exactly tair_sampler_prepare.  Otherwise 2 * batch <=
+ * max_batch, and ControlNet runs for both halves or neither (g->c_img without io->c_img is an error):
+ * TAIR_ERR_ARG with a message.  The scales are copied into a device table at a fixed address (this call
+ * waits for that copy on the host; tair_sampler_run never synchronises), so other scales need no new
+ * graph, while a guided and an unguided run never replay each other's.  After a guided prepare:
+ * tair_sampler_set_context re-encodes the cond half only (the negative context stays), tair_sampler_get_x
+ * returns the decoder features of the cond half (rows [0,B)), and tair_sampler_get_v the guided v. */
+int tair_sampler_prepare_guided(tair_cldm* h, const tair_sampler_io* io, const tair_guidance_io* g,
+                                tair_stream_t stream);
 /* Re-encodes the cross-attention K/V caches from a new c_txt (stage-3 val_sample, :317). */
 int tair_sampler_set_context(tair_cldm* h, const float* c_txt, int c_txt_batch, tair_stream_t stream);
 /* Runs n steps of p_sample (ControlNet + UNet + fused update) from the device step counter.

@@ -137,6 +137,22 @@ int tair_k_gn_apply_fp8(const void* x, int ldx, int x_lo, int B, int HW, int C, 
 /* GEGLU: [T, 2D] -> x * gelu(gate) (attention.py:19-26). */
 int tair_k_geglu(const void* xg, int T, int D, void* y, void* stream);
 
+/* One fused SpacedSampler update on caller-owned device buffers (spaced_sampler.py:141-189; the kernel
+ * tair_sampler_run launches per step), for a caller that drives its own loop:
+ *   v  = v_uncond ? v_uncond + scales[i] * (v - v_uncond) : v            (classifier-free guidance, :163)
+ *   x0 = tab0[t] x - tab1[t] v;  mean = tab2[t] x0 + tab3[t] x;  x = mean + [t != 0] sqrt(tab4[t]) noise[i]
+ * with i = counter[0] (loop index), n = counter[1] (steps of the schedule), t = n - 1 - i, all read on the
+ * device (the call is capturable and never synchronises; i outside [0, n) writes nothing; the caller
+ * advances the counter).  x [rows, C] fp32 NHWC in/out; v [rows, C] fp32, the guided v is written back to
+ * it when v_uncond is given; tables = the 5 rows of tair_sampler_set_schedule, [5][n]; scales [n] guidance
+ * scale per loop index (may be NULL without v_uncond); noise [n][rows, C].  The new x also leaves as
+ * (hi, lo, hi) bf16 planes, hi = bf16(x), lo = bf16(x - hi): in_u[row * ld + {0, C, 2C} + c] and, unless
+ * in_c is NULL, in_c[row * ld + {0, ldc, 2 ldc} + c]; half_rows > 0 writes the same planes again half_rows
+ * rows further on (the uncond half of a 2B-row model input).  Other channels of a row are left alone. */
+int tair_k_sampler_step(float* x, float* v, const float* v_uncond, const float* tables, const float* scales,
+                        const int* counter, const float* noise, int rows, int C, void* in_u, void* in_c, int ld,
+                        int ldc, int half_rows, void* stream);
+
 /* Overlap-blend stitch of decoded tiles on the device (val_patches.py:114-206 merge_patches_with_overlap,
  * stride generalised): tiles [n_tiles][C][patch][patch] fp32 on a raster nh x nw grid, out [C][H][W]
  * fp32 cropped; rtab[i] = fp32((i+1)/overlap), i < overlap (device).  Bitwise the reference loop. */

@@ -71,6 +71,16 @@ class SamplerIO(ctypes.Structure):
     ]
 
 
+class GuidanceIO(ctypes.Structure):
+    """tair_guidance_io: the negative-prompt half of a guided sampler run."""
+    _fields_ = [
+        ("c_txt", ctypes.c_void_p),
+        ("c_txt_batch", ctypes.c_int),
+        ("c_img", ctypes.c_void_p),
+        ("scales", ctypes.POINTER(ctypes.c_float)),
+    ]
+
+
 class GemmDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in ("M", "N", "K", "amode")] + [
         ("A", ctypes.c_void_p), ("lda", ctypes.c_int), ("C", ctypes.c_int), ("Bn", ctypes.c_int),
@@ -115,6 +125,7 @@ SIGNATURES = {
     "tair_cldm_forward": (_I, [_P, ctypes.POINTER(CldmIO), _P]),
     "tair_sampler_set_schedule": (_I, [_P, _I, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_float)]),
     "tair_sampler_prepare": (_I, [_P, ctypes.POINTER(SamplerIO), _P]),
+    "tair_sampler_prepare_guided": (_I, [_P, ctypes.POINTER(SamplerIO), ctypes.POINTER(GuidanceIO), _P]),
     "tair_sampler_set_context": (_I, [_P, _P, _I, _P]),
     "tair_sampler_run": (_I, [_P, _I, _I, _P]),
     "tair_sampler_get_x": (_I, [_P, _P, _P, _P]),
@@ -144,6 +155,7 @@ SIGNATURES = {
     "tair_k_geglu": (_I, [_P, _I, _I, _P, _P]),
     "tair_k_quant_rows_fp8_ex": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
     "tair_k_gn_apply_fp8": (_I, [_P, _I, _I, _I, _I, _I, _I, ctypes.c_float, _P, _P, _I, _P, _I, _P, _P, _I, _P]),
+    "tair_k_sampler_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P]),
     "tair_k_merge_overlap": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P]),
     "tair_k_stitch_peers": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P]),
     "tair_ipc_get_handle": (_I, [_P, _P, ctypes.POINTER(ctypes.c_ulonglong)]),

@@ -278,6 +278,8 @@ struct tair_cldm {
   int noise_cap_steps = 0;
   int64_t* sched_t_dev = nullptr;         // [n_steps] model timesteps of the schedule
   int s_batch = 0, s_ctx_bstride = 0, s_control = 0;
+  int s_guided = 0;                       // classifier-free guidance: the net runs 2 * s_batch rows, cond first
+  float* cfg_scales = nullptr;            // [tab_rows] guidance scale per loop index (fixed address: graph-safe)
   float s_scales[13];
   hipGraph_t graph = nullptr;
   hipGraphExec_t gexec = nullptr;
@@ -286,6 +288,7 @@ struct tair_cldm {
   hipEvent_t ev_in = nullptr, ev_out = nullptr;  // NULL) stream cannot be captured
   int graph_batch = -1;                   // what the captured step froze: batch, ControlNet on/off,
   int graph_control = -1, graph_ctx_bstride = -1;  // context batch stride and the zero-conv scales
+  int graph_guided = -1;                  // guided or not (the guidance scales are read from cfg_scales)
   float graph_scales[13] = {};
   // instrumentation
   bool dry = false;
@@ -1972,6 +1975,7 @@ int tair_cldm_create(const tair_cldm_cfg* cfg, tair_cldm** out) {
   h->rows_step = (int*)dmalloc(h, B * 4);
   h->counter = (int*)dmalloc(h, 16);
   h->xs = (float*)dmalloc(h, B * M0 * cfg->in_channels * 4);
+  h->cfg_scales = (float*)dmalloc(h, (size_t)h->tab_rows * 4);
   if (!cfg->manifest_only) {
     std::vector<int> iota(B);
     for (size_t i = 0; i < B; ++i) iota[i] = (int)i;
@@ -2433,34 +2437,6 @@ __global__ void init_counter_kernel(int* counter, int n) {
     counter[1] = n;
   }
 }
-// sampler update (spaced_sampler.py:141-189) fused with re-emitting the NHWC model inputs as (hi, lo, hi)
-// bf16 planes of the fp32 latent (in_u: rows of CONVIN_LD channels, planes C apart; in_c: planes ldc apart
-// with the latent at channels 0..C-1 of each plane)
-__global__ void step_update_kernel(float* xs, const float* v, const float* noise, const float* tabs,
-                                   const int* counter, int n, int C, bf16* in_u, bf16* in_c, int ldc) {
-  const int i = blockIdx.x * blockDim.x + threadIdx.x;
-  if (i >= n) return;
-  const int it = counter[0], ns = counter[1];
-  const int t = ns - 1 - it;
-  const float sa = tabs[t], s1a = tabs[ns + t], c1 = tabs[2 * ns + t], c2 = tabs[3 * ns + t], var = tabs[4 * ns + t];
-  const float xv = xs[i];
-  const float x0 = sa * xv - s1a * v[i];
-  const float mean = c1 * x0 + c2 * xv;
-  const float xn = (t != 0) ? mean + sqrtf(var) * noise[(size_t)it * n + i] : mean;
-  xs[i] = xn;
-  const int row = i / C, c = i - row * C;
-  const bf16 hi = (bf16)xn, lo = (bf16)(xn - (float)hi);
-  bf16* u = in_u + (size_t)row * CONVIN_LD + c;
-  u[0] = hi;
-  u[C] = lo;
-  u[2 * C] = hi;
-  if (in_c) {
-    bf16* q = in_c + (size_t)row * CONVIN_LD + c;
-    q[0] = hi;
-    q[ldc] = lo;
-    q[2 * ldc] = hi;
-  }
-}
 // NCHW [B,C,HW] fp32 -> NHWC [B*HW, C] fp32
 __global__ void nchw2nhwc_f32_kernel(const float* x, int B, int C, int HW, float* y) {
   const long i = blockIdx.x * (long)blockDim.x + threadIdx.x;
@@ -2472,7 +2448,19 @@ __global__ void nchw2nhwc_f32_kernel(const float* x, int B, int C, int HW, float
 }
 }  // namespace
 
-int tair_sampler_prepare(tair_cldm* h, const tair_sampler_io* io, tair_stream_t stream) {
+// The bf16 context rows of tiles [slot0, slot0 + B): a broadcast context (cb == 1) is written once per tile, so
+// that a guided run's two halves, each broadcast or per tile, share the per-tile K/V layout.
+static hipError_t put_ctx_tiles(tair_cldm* h, const float* c_txt, int cb, int B, int slot0, hipStream_t s) {
+  const size_t per = (size_t)h->cfg.context_len * h->cfg.context_dim;
+  bf16* dst = h->ctx_bf + (size_t)slot0 * per;
+  if (cb == B) return launch(h, 4, 0, s, [&] { return f32_to_bf16(c_txt, (int)(B * per), dst, s); });
+  for (int b = 0; b < B; ++b)
+    TRY(launch(h, 4, 0, s, [&] { return f32_to_bf16(c_txt, (int)per, dst + (size_t)b * per, s); }));
+  return hipSuccess;
+}
+
+int tair_sampler_prepare_guided(tair_cldm* h, const tair_sampler_io* io, const tair_guidance_io* g,
+                                tair_stream_t stream) {
   tair::g_err[0] = 0;
   int rc = check_ready(h);
   if (rc) return rc;
@@ -2485,20 +2473,58 @@ int tair_sampler_prepare(tair_cldm* h, const tair_sampler_io* io, tair_stream_t 
     set_error("sampler_prepare: bad io");
     return TAIR_ERR_ARG;
   }
+  if (g) {
+    if (2 * io->batch > h->cfg.max_batch) {
+      set_error("sampler_prepare_guided: guidance runs 2 x batch rows: batch %d needs max_batch >= %d (is %d)",
+                io->batch, 2 * io->batch, h->cfg.max_batch);
+      return TAIR_ERR_ARG;
+    }
+    if (!g->c_txt || !g->scales || (g->c_txt_batch != 1 && g->c_txt_batch != io->batch)) {
+      set_error("sampler_prepare_guided: bad guidance (c_txt %p, scales %p, c_txt_batch %d, batch %d)",
+                (const void*)g->c_txt, (const void*)g->scales, g->c_txt_batch, io->batch);
+      return TAIR_ERR_ARG;
+    }
+    if (g->c_img && !io->c_img) {
+      set_error("sampler_prepare_guided: the uncond half has a c_img and the cond half none (ControlNet runs for "
+                "both halves or for neither)");
+      return TAIR_ERR_ARG;
+    }
+  }
   hipStream_t s = (hipStream_t)stream;
   const int B = io->batch;
   const int HW = h->lev_h[0] * h->lev_w[0];
-  const int C = h->cfg.in_channels;
+  const int C = h->cfg.in_channels, hc = h->cfg.hint_channels;
   h->s_batch = B;
-  h->s_ctx_bstride = io->c_txt_batch == 1 ? 0 : h->cfg.context_len;
+  h->s_guided = g != nullptr;
+  h->s_ctx_bstride = (g || io->c_txt_batch != 1) ? h->cfg.context_len : 0;
   h->s_control = io->c_img != nullptr;
   for (int i = 0; i < 13; ++i) h->s_scales[i] = io->control_scales ? io->control_scales[i] : 1.f;
   auto run = [&]() -> hipError_t {
     // time-embedding tables for every step of the schedule: one batched GEMM chain per net
     TRY(time_tables(h, h->unet, h->sched_t_dev, h->n_steps, h->tab_u, s));
     if (h->s_control) TRY(time_tables(h, h->cn, h->sched_t_dev, h->n_steps, h->tab_c, s));
-    TRY(prepare_ctx(h, io->c_txt, io->c_txt_batch, s));
+    if (g) {  // rows [0, B) cond, [B, 2B) uncond: contexts, K/V caches and conv_in planes for both halves
+      TRY(put_ctx_tiles(h, io->c_txt, io->c_txt_batch, B, 0, s));
+      TRY(put_ctx_tiles(h, g->c_txt, g->c_txt_batch, B, B, s));
+      TRY(kv_caches(h, h->unet, 2 * B * h->cfg.context_len, s));
+      TRY(kv_caches(h, h->cn, 2 * B * h->cfg.context_len, s));
+    } else {
+      TRY(prepare_ctx(h, io->c_txt, io->c_txt_batch, s));
+    }
     TRY(prepare_inputs(h, B, io->x_T, io->c_img, s));
+    if (g) {
+      const size_t half = (size_t)B * HW * CONVIN_LD;
+      TRY(launch(h, 4, 0, s, [&] { return nchw_split(io->x_T, B, C, HW, h->in_u + half, CONVIN_LD, 0, C, s); }));
+      if (h->s_control) {
+        const float* img = g->c_img ? g->c_img : io->c_img;
+        TRY(launch(h, 4, 0, s, [&] { return nchw_split(io->x_T, B, C, HW, h->in_c + half, CONVIN_LD, 0, C + hc, s); }));
+        TRY(launch(h, 4, 0, s, [&] { return nchw_split(img, B, hc, HW, h->in_c + half, CONVIN_LD, C, C + hc, s); }));
+      }
+      // the guidance scales live at a fixed device address that the captured step reads: new values need
+      // no new graph (synchronises on the host copy, as set_schedule does; tair_sampler_run never does)
+      TRY(hipMemcpyAsync(h->cfg_scales, g->scales, (size_t)h->n_steps * 4, hipMemcpyHostToDevice, s));
+      TRY(hipStreamSynchronize(s));
+    }
     const long n = (long)B * C * HW;
     hipLaunchKernelGGL(nchw2nhwc_f32_kernel, dim3((n + 255) / 256), dim3(256), 0, s, io->x_T, B, C, HW, h->xs);
     TRY(hipGetLastError());
@@ -2514,6 +2540,10 @@ int tair_sampler_prepare(tair_cldm* h, const tair_sampler_io* io, tair_stream_t 
   return TAIR_OK;
 }
 
+int tair_sampler_prepare(tair_cldm* h, const tair_sampler_io* io, tair_stream_t stream) {
+  return tair_sampler_prepare_guided(h, io, nullptr, stream);
+}
+
 int tair_sampler_set_context(tair_cldm* h, const float* c_txt, int c_txt_batch, tair_stream_t stream) {
   tair::g_err[0] = 0;
   int rc = check_ready(h);
@@ -2522,31 +2552,53 @@ int tair_sampler_set_context(tair_cldm* h, const float* c_txt, int c_txt_batch, 
     set_error("set_context: bad arguments");
     return TAIR_ERR_ARG;
   }
-  if ((c_txt_batch == 1 ? 0 : h->cfg.context_len) != h->s_ctx_bstride) {
-    set_error("set_context: context batch layout changed since prepare");
-    return TAIR_ERR_ARG;
+  hipStream_t s = (hipStream_t)stream;
+  hipError_t e;
+  if (h->s_guided) {  // the cond half only (tiles [0, B), always laid out per tile); the negative context stays
+    const int B = h->s_batch;
+    auto run = [&]() -> hipError_t {
+      TRY(put_ctx_tiles(h, c_txt, c_txt_batch, B, 0, s));
+      TRY(kv_caches(h, h->unet, B * h->cfg.context_len, s));
+      return kv_caches(h, h->cn, B * h->cfg.context_len, s);
+    };
+    e = run();
+  } else {
+    if ((c_txt_batch == 1 ? 0 : h->cfg.context_len) != h->s_ctx_bstride) {
+      set_error("set_context: context batch layout changed since prepare");
+      return TAIR_ERR_ARG;
+    }
+    e = prepare_ctx(h, c_txt, c_txt_batch, s);
   }
-  hipError_t e = prepare_ctx(h, c_txt, c_txt_batch, (hipStream_t)stream);
   if (e != hipSuccess) return fail_hip(e);
   return TAIR_OK;
 }
 
 static hipError_t sampler_one_step(tair_cldm* h, hipStream_t s) {
   const int B = h->s_batch;
+  const int nb = h->s_guided ? 2 * B : B;  // rows the net runs: cond [0, B), uncond [B, 2B)
   const int HW = h->lev_h[0] * h->lev_w[0];
   const int C = h->cfg.in_channels;
-  hipLaunchKernelGGL(set_rows_kernel, dim3(1), dim3(std::max(64, ((B + 63) / 64) * 64)), 0, s, h->counter,
-                     h->rows_step, B);
+  hipLaunchKernelGGL(set_rows_kernel, dim3(1), dim3(std::max(64, ((nb + 63) / 64) * 64)), 0, s, h->counter,
+                     h->rows_step, nb);
   TRY(hipGetLastError());
-  const Fwd f = make_fwd(h, s, B, h->rows_step, h->s_ctx_bstride, h->s_control);
+  const Fwd f = make_fwd(h, s, nb, h->rows_step, h->s_ctx_bstride, h->s_control);
   TRY(body(h, f, h->s_control, h->s_scales));
-  const int n = B * HW * C;
-  TRY(launch(h, 4, 0, s, [&] {
-    hipLaunchKernelGGL(step_update_kernel, dim3((n + 255) / 256), dim3(256), 0, s, h->xs, h->v_out, h->noise,
-                       h->sched_tabs, h->counter, n, C, h->in_u, h->s_control ? h->in_c : (bf16*)nullptr,
-                       C + h->cfg.hint_channels);
-    return hipGetLastError();
-  }));
+  SamplerUpdateArgs u{};
+  u.x = h->xs;
+  u.v = h->v_out;
+  u.v_u = h->s_guided ? h->v_out + (size_t)B * HW * C : nullptr;
+  u.tabs = h->sched_tabs;
+  u.scales = h->cfg_scales;
+  u.counter = h->counter;
+  u.noise = h->noise;
+  u.rows = B * HW;
+  u.C = C;
+  u.in_u = h->in_u;
+  u.in_c = h->s_control ? h->in_c : nullptr;
+  u.ld = CONVIN_LD;
+  u.ldc = C + h->cfg.hint_channels;
+  u.half_rows = h->s_guided ? B * HW : 0;
+  TRY(launch(h, 4, 0, s, [&] { return sampler_update(u, s); }));
   hipLaunchKernelGGL(advance_kernel, dim3(1), dim3(64), 0, s, h->counter);
   return hipGetLastError();
 }
@@ -2574,9 +2626,10 @@ int tair_sampler_run(tair_cldm* h, int n_steps, int use_graph, tair_stream_t str
     if (e == hipSuccess) e = hipStreamWaitEvent(s, h->ev_in, 0);
     if (e != hipSuccess) return fail_hip(e);
     // the captured step bakes in the batch, whether the ControlNet branch runs, the context batch
-    // stride and the control scales (GEMM alpha): any change since the capture needs a new graph
+    // stride, guided or not (2B rows and the guided update; the guidance scales themselves are read from
+    // a device table) and the control scales (GEMM alpha): any change since the capture needs a new graph
     const bool same = h->gexec != nullptr && h->graph_batch == h->s_batch && h->graph_control == h->s_control &&
-                      h->graph_ctx_bstride == h->s_ctx_bstride &&
+                      h->graph_ctx_bstride == h->s_ctx_bstride && h->graph_guided == h->s_guided &&
                       std::memcmp(h->graph_scales, h->s_scales, sizeof(h->s_scales)) == 0;
     if (!same) drop_step_graphs(h);
     if (!same) {
@@ -2596,6 +2649,7 @@ int tair_sampler_run(tair_cldm* h, int n_steps, int use_graph, tair_stream_t str
       h->graph_batch = h->s_batch;
       h->graph_control = h->s_control;
       h->graph_ctx_bstride = h->s_ctx_bstride;
+      h->graph_guided = h->s_guided;
       std::memcpy(h->graph_scales, h->s_scales, sizeof(h->s_scales));
     }
     for (int i = 0; i < n_steps; ++i) {

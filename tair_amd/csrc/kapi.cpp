@@ -148,6 +148,19 @@ int tair_k_geglu(const void* xg, int T, int D, void* y, void* stream) {
   return geglu((const bf16*)xg, T, D, (bf16*)y, (hipStream_t)stream) == hipSuccess ? 0 : -2;
 }
 
+int tair_k_sampler_step(float* x, float* v, const float* v_uncond, const float* tables, const float* scales,
+                        const int* counter, const float* noise, int rows, int C, void* in_u, void* in_c, int ld,
+                        int ldc, int half_rows, void* stream) {
+  SamplerUpdateArgs a{x, v, v_uncond, tables, scales, counter, noise, rows, C, (bf16*)in_u, (bf16*)in_c, ld, ldc,
+                      half_rows};
+  const hipError_t e = sampler_update(a, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) {
+    set_error("sampler_step: bad arguments (rows %d, C %d, ld %d, ldc %d, half_rows %d)", rows, C, ld, ldc, half_rows);
+    return -1;
+  }
+  return e == hipSuccess ? 0 : -2;
+}
+
 int tair_k_merge_overlap(const float* tiles, int n_tiles, int nh, int nw, int patch, int overlap, int stride,
                          float* out, int C, int H, int W, const float* rtab, void* stream) {
   return merge_overlap(tiles, n_tiles, nh, nw, patch, overlap, stride, out, C, H, W, rtab, (hipStream_t)stream) ==

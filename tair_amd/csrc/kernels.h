@@ -301,6 +301,21 @@ hipError_t stitch_peers(const float* const* src, int per_rank, int first_image, 
 // v-parameterised ancestral step (spaced_sampler.py:141-189), tables indexed on device
 hipError_t sampler_step_v(const float* x, const float* v, const float* noise, const float* tabs,
                           const int* step_idx, int n, float* x_out, hipStream_t s);
+// The fused loop's sampler update (spaced_sampler.py:141-189, guidance :163) on the device step counter:
+//   v = v_u ? v_u + scales[i] (v - v_u) : v;  x0 = tab0[t] x - tab1[t] v;  mean = tab2[t] x0 + tab3[t] x;
+//   x' = mean + [t != 0] sqrt(tab4[t]) noise[i],  i = counter[0], t = counter[1] - 1 - i
+// x [rows, C] fp32 in/out; v [rows, C] (the guided v is written back when v_u is given); tabs [5][n_steps];
+// noise [n_steps][rows, C].  x' is re-emitted as (hi, lo, hi) bf16 planes: in_u[row * ld + {0, C, 2C} + c],
+// in_c (optional) [row * ld + {0, ldc, 2 ldc} + c], and again half_rows rows further on when half_rows > 0
+// (the uncond half of a 2B-row model input).  No host synchronisation; capturable.
+struct SamplerUpdateArgs {
+  float* x; float* v; const float* v_u;
+  const float* tabs; const float* scales; const int* counter; const float* noise;
+  int rows, C;
+  bf16* in_u; bf16* in_c; int ld, ldc;
+  int half_rows;
+};
+hipError_t sampler_update(const SamplerUpdateArgs& a, hipStream_t s);
 
 // Multi-scale deformable attention sampling (TESTR, msda.hip): level shapes by value (capturable)
 constexpr int MSDA_MAX_LEVELS = 8;

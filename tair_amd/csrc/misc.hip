@@ -105,6 +105,58 @@ __global__ void sampler_step_kernel(const float* __restrict__ x, const float* __
   xo[i] = (t != 0) ? mean + sqrtf(var) * noise[i] : mean;
 }
 
+// The sampler update of the fused loop (spaced_sampler.py:141-189), one thread per latent element of the
+// [rows, C] fp32 state, fused with re-emitting the NHWC model inputs as (hi, lo, hi) bf16 planes of the new
+// latent (in_u: rows of ld channels, planes C apart; in_c: planes ldc apart with the latent at channels
+// 0..C-1 of each plane).  counter = {loop index, n_steps}; t = n_steps - 1 - index selects the table column.
+// v_u != null is classifier-free guidance (spaced_sampler.py:163): v = v_u + s (v_c - v_u) with s =
+// scales[loop index]; the guided v replaces v_c in place (what p_sample consumed) and the planes also go
+// to the uncond half of the 2B-row model input, half_off elements further on.  With v_u == null the
+// arithmetic is the unguided update's, bit for bit.  An index outside [0, n_steps) writes nothing.
+__global__ void sampler_update_kernel(float* xs, float* v, const float* v_u, const float* noise, const float* tabs,
+                                      const float* scales, const int* counter, int n, int C, bf16* in_u, bf16* in_c,
+                                      int ld, int ldc, size_t half_off) {
+  const int i = blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= n) return;
+  const int it = counter[0], ns = counter[1];
+  if (it < 0 || it >= ns) return;
+  const int t = ns - 1 - it;
+  const float sa = tabs[t], s1a = tabs[ns + t], c1 = tabs[2 * ns + t], c2 = tabs[3 * ns + t], var = tabs[4 * ns + t];
+  float vi = v[i];
+  if (v_u) {
+    const float vu = v_u[i];
+    vi = vu + scales[it] * (vi - vu);
+    v[i] = vi;
+  }
+  const float xv = xs[i];
+  const float x0 = sa * xv - s1a * vi;
+  const float mean = c1 * x0 + c2 * xv;
+  const float xn = (t != 0) ? mean + sqrtf(var) * noise[(size_t)it * n + i] : mean;
+  xs[i] = xn;
+  const int row = i / C, c = i - row * C;
+  const bf16 hi = (bf16)xn, lo = (bf16)(xn - (float)hi);
+  bf16* u = in_u + (size_t)row * ld + c;
+  u[0] = hi;
+  u[C] = lo;
+  u[2 * C] = hi;
+  if (half_off) {
+    u[half_off] = hi;
+    u[half_off + C] = lo;
+    u[half_off + 2 * C] = hi;
+  }
+  if (in_c) {
+    bf16* q = in_c + (size_t)row * ld + c;
+    q[0] = hi;
+    q[ldc] = lo;
+    q[2 * ldc] = hi;
+    if (half_off) {
+      q[half_off] = hi;
+      q[half_off + ldc] = lo;
+      q[half_off + 2 * ldc] = hi;
+    }
+  }
+}
+
 }  // namespace
 
 static inline int blocks_for(long n, int bs) { return (int)((n + bs - 1) / bs); }
@@ -156,6 +208,17 @@ hipError_t nhwc_bf16_to_nchw_f32(const bf16* x, int ldx, int B, int C, int HW, f
 hipError_t nhwc_f32_to_nchw_f32(const float* x, int B, int C, int HW, float* y, hipStream_t s) {
   const long total = (long)B * C * HW;
   hipLaunchKernelGGL(nhwcf2nchw_kernel, dim3(blocks_for(total, 256)), dim3(256), 0, s, x, B, C, HW, y);
+  return hipGetLastError();
+}
+
+hipError_t sampler_update(const SamplerUpdateArgs& a, hipStream_t s) {
+  if (!a.x || !a.v || !a.tabs || !a.counter || !a.noise || !a.in_u || a.rows < 1 || a.C < 1 || a.ld < 3 * a.C ||
+      a.half_rows < 0 || (a.v_u && !a.scales) || (a.in_c && (a.ldc < a.C || 2 * a.ldc + a.C > a.ld)) ||
+      (long)a.rows * a.C > 0x7fffffffL)
+    return hipErrorInvalidValue;
+  const int n = a.rows * a.C;
+  hipLaunchKernelGGL(sampler_update_kernel, dim3(blocks_for(n, 256)), dim3(256), 0, s, a.x, a.v, a.v_u, a.noise,
+                     a.tabs, a.scales, a.counter, n, a.C, a.in_u, a.in_c, a.ld, a.ldc, (size_t)a.half_rows * a.ld);
   return hipGetLastError();
 }
 

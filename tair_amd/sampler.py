@@ -1,9 +1,14 @@
 """SpacedSampler drop-in (reference: terediff/sampler/spaced_sampler.py:67-328, sampler.py:10-38).
 
-``sample`` / ``val_sample`` keep the reference signatures.  With ``uncond is None or cfg_scale == 1``
-(the only mode the val drivers use, val_patches.py:334-348) the whole 50-step loop runs inside
+``sample`` / ``val_sample`` keep the reference signatures.  The whole 50-step loop runs inside
 libtair_cldm.so: ControlNet + UNet + the fused p_sample update are captured once into a hipGraph
 and replayed per step with a device-side step counter (no host round trip per step).
+
+Classifier-free guidance (``uncond`` given and ``cfg_scale != 1``, pipeline.py's negative prompt) runs in
+the same graph: one forward at batch 2B per step (cond rows, then uncond rows) and the update kernel
+combines the halves with the step's guidance scale from a device table.  That needs ``2B <= max_batch``;
+otherwise ``sample`` falls back to the host loop ``_sample_cfg`` (two eager forwards per step) and
+``val_sample`` raises.  ``last_guided_fused`` tells which path a guided ``sample`` took.
 
 Noise: the reference draws ``randn_like(x)`` from the global RNG inside every p_sample
 (spaced_sampler.py:186).  Here the per-step noise is an explicit ``noise=[steps, B, 4, h, w]``
@@ -54,6 +59,7 @@ class SpacedSampler:
         self.rescale_cfg = rescale_cfg
         self.timesteps = None
         self.tables: Dict[str, np.ndarray] = {}
+        self.last_guided_fused: Optional[bool] = None  # the last `sample`: guided in the step graph (None: unguided)
 
     # sampler.py:31-38
     def get_cfg_scale(self, default_cfg_scale: float, model_t: int) -> float:
@@ -73,9 +79,20 @@ class SpacedSampler:
         rows += ["posterior_mean_coef1", "posterior_mean_coef2", "posterior_variance"]
         return np.ascontiguousarray(np.stack([self.tables[r] for r in rows]).astype(np.float32))
 
+    def _guidance_scales(self, cfg_scale: float, steps: int) -> np.ndarray:
+        """float32 [steps]: get_cfg_scale at the model timestep of loop index i (spaced_sampler.py:224-235),
+        the table the guided update kernel reads on the device."""
+        ts = np.flip(spaced_tables(self.training_betas, steps)[0])
+        return np.asarray([self.get_cfg_scale(cfg_scale, int(t)) for t in ts], dtype=np.float32)
+
+    @staticmethod
+    def _guided(uncond, cfg_scale: float) -> bool:
+        return uncond is not None and cfg_scale != 1.0
+
     # ------------------------------------------------------------------ fused path
     def _setup(self, model: ControlLDM, steps: int, x_T: torch.Tensor, cond: Dict[str, torch.Tensor],
-               noise: Optional[torch.Tensor]):
+               noise: Optional[torch.Tensor], uncond: Optional[Dict[str, torch.Tensor]] = None,
+               cfg_scales: Optional[np.ndarray] = None):
         if self.parameterization not in ("v", "eps"):
             raise NotImplementedError(f"parameterization {self.parameterization!r} (spaced_sampler.py:182-185: v or eps)")
         self.make_schedule(steps)
@@ -107,7 +124,29 @@ class SpacedSampler:
         scales = _lib.float_array(model.control_scales)
         io.control_scales = ctypes.cast(scales, ctypes.POINTER(ctypes.c_float))
         self._keep = (x_T, noise, c_txt, c_img)  # alive until prepare's kernels ran
-        _lib.check(L.tair_sampler_prepare(model._h, ctypes.byref(io), _stream_ptr(dev)), "sampler_prepare")
+        if uncond is None:
+            _lib.check(L.tair_sampler_prepare(model._h, ctypes.byref(io), _stream_ptr(dev)), "sampler_prepare")
+            return B
+        # guided: the negative prompt's half; c_img NULL = the cond's (the usual case: same storage)
+        u_txt = uncond["c_txt"].detach().to(device=dev, dtype=torch.float32).contiguous()
+        u_img = uncond.get("c_img")
+        if u_img is not None:
+            same = cond.get("c_img") is not None and u_img.data_ptr() == cond["c_img"].data_ptr() \
+                and u_img.shape == cond["c_img"].shape and u_img.stride() == cond["c_img"].stride()
+            u_img = None if same else u_img.detach().to(device=dev, dtype=torch.float32).contiguous()
+        elif c_img is not None:
+            raise ValueError("guided sampling: uncond has no c_img and cond has one (ControlNet runs for both or neither)")
+        cfg_scales = np.ascontiguousarray(cfg_scales, dtype=np.float32)
+        if cfg_scales.shape != (steps,):
+            raise ValueError(f"guidance scales must be [{steps}], got {cfg_scales.shape}")
+        g = _lib.GuidanceIO()
+        g.c_txt = u_txt.data_ptr()
+        g.c_txt_batch = u_txt.shape[0]
+        g.c_img = None if u_img is None else u_img.data_ptr()
+        g.scales = cfg_scales.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
+        self._keep += (u_txt, u_img)
+        _lib.check(L.tair_sampler_prepare_guided(model._h, ctypes.byref(io), ctypes.byref(g), _stream_ptr(dev)),
+                   "sampler_prepare_guided")
         return B
 
     def _run(self, model: ControlLDM, n: int, use_graph: bool, dev):
@@ -133,11 +172,18 @@ class SpacedSampler:
 
     @torch.no_grad()
     def sample_trace(self, model: ControlLDM, steps: int, x_T: torch.Tensor, cond: Dict[str, torch.Tensor],
-                     noise: torch.Tensor, use_graph: bool = True):
+                     noise: torch.Tensor, use_graph: bool = True, uncond: Optional[Dict[str, torch.Tensor]] = None,
+                     cfg_scale: float = 1.0):
         """The fused loop of `sample`, one step per launch, recording per step (x_t, v, x0_hat) with
         x0_hat = _predict_xstart_from_v (spaced_sampler.py:141-147): parity instrumentation for the
-        per-step check against the oracle (same kernels and graph as `sample`)."""
-        self._setup(model, steps, x_T, cond, noise)
+        per-step check against the oracle (same kernels and graph as `sample`).  With `uncond` and
+        `cfg_scale != 1` the guided fused loop is traced; v is then the guided v."""
+        if self._guided(uncond, cfg_scale):
+            if 2 * x_T.shape[0] > model.max_batch:
+                raise ValueError(f"guided sample_trace: batch {x_T.shape[0]} needs max_batch >= {2 * x_T.shape[0]}")
+            self._setup(model, steps, x_T, cond, noise, uncond, self._guidance_scales(cfg_scale, steps))
+        else:
+            self._setup(model, steps, x_T, cond, noise)
         dev, shape = x_T.device, tuple(x_T.shape)
         eps = self.parameterization == "eps"  # x0_hat from the model output as p_sample forms it
         sa = self.tables["sqrt_recip_alphas_cumprod" if eps else "sqrt_alphas_cumprod"].astype(np.float32)
@@ -164,7 +210,9 @@ class SpacedSampler:
             raise NotImplementedError("latent tiling is out of scope (SURVEY §2)")
         if x_T is None:
             x_T = torch.randn(x_size, device=device, dtype=torch.float32)
-        if uncond is not None and cfg_scale != 1.0:
+        guided = self._guided(uncond, cfg_scale)
+        self.last_guided_fused = (2 * x_T.shape[0] <= model.max_batch) if guided else None
+        if guided and not self.last_guided_fused:  # no room for 2B rows: two eager forwards per step on the host
             return self._sample_cfg(model, steps, x_T, cond, uncond, cfg_scale, noise)
         feat_steps = []
         if cfg is not None:
@@ -172,7 +220,10 @@ class SpacedSampler:
                 feat_steps = sorted(int(s) for s in cfg.exp_args["unet_feat_sampling_timestep"])
             except (AttributeError, KeyError, TypeError):
                 feat_steps = []
-        self._setup(model, steps, x_T, cond, noise)
+        if guided:
+            self._setup(model, steps, x_T, cond, noise, uncond, self._guidance_scales(cfg_scale, steps))
+        else:
+            self._setup(model, steps, x_T, cond, noise)
         dev = x_T.device
         ts_desc = np.flip(self.timesteps)
         sampled = []
@@ -197,7 +248,9 @@ class SpacedSampler:
                    decode_fn: Optional[Callable] = None, prompt_style: str = "CAPTION", use_graph: bool = True,
                    graph_prompt_path: bool = True):
         """spaced_sampler.py:245-328: per step, TESTR reads the decoder features, the recognised text
-        becomes the next cross-attention prompt (stock PyTorch; K/V caches re-encoded in place)."""
+        becomes the next cross-attention prompt (stock PyTorch; K/V caches re-encoded in place).  With
+        `uncond` and `cfg_scale != 1` every step is guided in the step graph (the features TESTR reads are the
+        cond half's, and the new prompt replaces the cond context only); that needs 2B <= max_batch."""
         assert ts_model is not None, "Text-spotting model must be provided for validation sampling."
         if x_T is None:
             x_T = torch.randn(x_size, device=device, dtype=torch.float32)
@@ -222,7 +275,13 @@ class SpacedSampler:
         B = x_T.shape[0]
         if B > 1 and cond["c_txt"].shape[0] == 1:  # per-tile prompts from step 1 on: per-tile context layout
             cond = dict(cond, c_txt=cond["c_txt"].expand(B, -1, -1))
-        self._setup(model, steps, x_T, cond, noise)
+        if self._guided(uncond, cfg_scale):
+            if 2 * B > model.max_batch:
+                raise ValueError(f"guided val_sample runs 2 x batch rows per step: batch {B} needs max_batch >= "
+                                 f"{2 * B} (is {model.max_batch})")
+            self._setup(model, steps, x_T, cond, noise, uncond, self._guidance_scales(cfg_scale, steps))
+        else:
+            self._setup(model, steps, x_T, cond, noise)
         dev = x_T.device
         ts_desc = np.flip(self.timesteps)
         results = []
@@ -253,7 +312,8 @@ class SpacedSampler:
         _check_device_faults(dev, "SpacedSampler.val_sample")
         return x, results
 
-    # classifier-free guidance (two forwards per step; not used by the val drivers)
+    # classifier-free guidance on the host (two eager forwards per step): `sample`'s fallback when the handle
+    # has no room for 2B rows, and the baseline tools/cfg_bench.py measures the fused path against
     def _sample_cfg(self, model, steps, x_T, cond, uncond, cfg_scale, noise):
         self.make_schedule(steps)
         dev = x_T.device
