@@ -134,6 +134,13 @@ int tair_k_quant_rows_fp8_ex(const void* w, int rows, int K, int Kx, int ldw, co
 int tair_k_gn_apply_fp8(const void* x, int ldx, int x_lo, int B, int HW, int C, int G, float eps, const float* gamma,
                         const float* beta, int silu, const double* st, int st_rs, const float* inv8, void* y8, int ld8,
                         void* stream);
+/* Host routine (no device work): the composed FF-out + proj_out weight of a SpatialTransformer as finalize packs it.
+ * wpout [C][C], wff2 [C][4C], bff2 [C], bpout [C] fp32 -> packed [C][ldp] bf16 bits (ldp >= 5C; row n holds
+ * sum_j wpout[n][j] wff2[j][k] for k < 4C, then wpout[n][k - 4C] for 4C <= k < 5C, zeros beyond) and bias [C] =
+ * wpout . bff2 + bpout.  The GEMM reads it with K = 4C against the GEGLU output and Kx = C against the
+ * transformer stream. */
+int tair_k_compose_ffpout(const float* wpout, const float* wff2, const float* bff2, const float* bpout, int C,
+                          void* packed, int ldp, float* bias);
 /* GEGLU: [T, 2D] -> x * gelu(gate) (attention.py:19-26). */
 int tair_k_geglu(const void* xg, int T, int D, void* y, void* stream);
 

@@ -153,6 +153,7 @@ SIGNATURES = {
     "tair_k_layernorm_fp8": (_I, [_P, _I, _I, _P, _P, ctypes.c_float, _P, _I, _P, _P]),
     "tair_k_quant_rows_fp8": (_I, [_P, _I, _I, _I, _P, _I, _P, _P]),
     "tair_k_geglu": (_I, [_P, _I, _I, _P, _P]),
+    "tair_k_compose_ffpout": (_I, [_P, _P, _P, _P, _I, _P, _I, _P]),
     "tair_k_quant_rows_fp8_ex": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
     "tair_k_gn_apply_fp8": (_I, [_P, _I, _I, _I, _I, _I, _I, ctypes.c_float, _P, _P, _I, _P, _I, _P, _P, _I, _P]),
     "tair_k_sampler_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P]),

@@ -8,6 +8,7 @@
 // decoder block 11-i (torch.cat([h, hs.pop()+control.pop()]) in controlnet.py:50), the ControlNet
 // zero-conv epilogue accumulates its control residual into the same columns in place, and each
 // decoder block writes its output into the left-hand channels of the next concat buffer.
+#include <atomic>
 #include <cmath>
 #include <cstdarg>
 #include <cstdio>
@@ -19,6 +20,7 @@
 #include <mutex>
 #include <set>
 #include <string>
+#include <thread>
 #include <vector>
 
 #include "kernels.h"
@@ -139,6 +141,12 @@ struct STW {
   bool fold = false;
   std::string tb;  // state-dict prefix of the transformer block
   int fb_qkv = 0, fb_q2 = 0, fb_ff1 = 0, cs_qkv = 0, cs_q2 = 0, cs_ff1 = 0;
+  // FF-out composed with proj_out: fpo = [Wpout Wff2 | Wpout] as [C][4C + C], read against
+  // [F | X2] (the K-extension columns), and its bias Wpout b_ff2 + b_pout at arena offset fpob; built at finalize
+  // from the fp32 rows of ff.net.2 / proj_out (kept: either may be loaded again alone).  No backing parameter.
+  Weight fpo;
+  int fpob = 0;
+  std::string pfx;  // state-dict prefix of the SpatialTransformer
 };
 
 struct ConvW {
@@ -195,6 +203,64 @@ struct ProfRec {
   double alg;       // algorithmic bytes of the launch: operands read once, outputs written once
   std::string key;  // kernel family key (tools/pmc_summary.py joins it to the PMC rows' kernel names)
 };
+
+// kernels.h: [Wpout Wff2 | Wpout] and Wpout b_ff2 + b_pout.  One task = 16 rows x 256 product columns; the
+// fp32 accumulators of a task (16 KB) stay in L1 while the 64 Wff2 row segments of a block stream through
+void compose_ffpout(const float* wpout, const float* wff2, const float* bff2, const float* bpout, int C,
+                    uint16_t* packed, int ldp, float* bias) {
+  constexpr int NB = 16, KB = 256, JB = 64;
+  const int K4 = 4 * C;
+  const int nkb = (K4 + KB - 1) / KB;
+  const long ntask = (long)((C + NB - 1) / NB) * nkb;
+  auto task = [&](long t) {
+    const int n0 = (int)(t / nkb) * NB, k0 = (int)(t % nkb) * KB;
+    const int nn = std::min(NB, C - n0), kk = std::min(KB, K4 - k0);
+    std::vector<double> dacc((size_t)NB * KB, 0.0);
+    float acc[NB][KB];
+    for (int j0 = 0; j0 < C; j0 += JB) {
+      const int j1 = std::min(j0 + JB, C);
+      for (int r = 0; r < nn; ++r) std::memset(acc[r], 0, (size_t)kk * sizeof(float));
+      for (int j = j0; j < j1; ++j) {
+        const float* wr = wff2 + (size_t)j * K4 + k0;
+        for (int r = 0; r < nn; ++r) {
+          const float p = wpout[(size_t)(n0 + r) * C + j];
+          float* a = acc[r];
+          for (int k = 0; k < kk; ++k) a[k] += p * wr[k];
+        }
+      }
+      for (int r = 0; r < nn; ++r)
+        for (int k = 0; k < kk; ++k) dacc[(size_t)r * KB + k] += acc[r][k];
+    }
+    for (int r = 0; r < nn; ++r)
+      for (int k = 0; k < kk; ++k)
+        packed[(size_t)(n0 + r) * ldp + k0 + k] = f2bf_bits((float)dacc[(size_t)r * KB + k]);
+  };
+  // small products (the tiny configurations the tests create by the dozen) run inline
+  const unsigned hw = std::thread::hardware_concurrency();
+  const int nthr = C < 256 ? 1 : (int)std::min<long>(ntask, std::min(16u, hw ? hw : 1u));
+  if (nthr <= 1) {
+    for (long t = 0; t < ntask; ++t) task(t);
+  } else {
+    std::atomic<long> next{0};
+    std::vector<std::thread> pool;
+    for (int i = 0; i < nthr; ++i)
+      pool.emplace_back([&] {
+        for (long t; (t = next.fetch_add(1)) < ntask;) task(t);
+      });
+    for (auto& th : pool) th.join();
+  }
+  for (int n = 0; n < C; ++n) {
+    uint16_t* row = packed + (size_t)n * ldp;
+    const float* pr = wpout + (size_t)n * C;
+    double b = bpout[n];
+    for (int j = 0; j < C; ++j) {
+      row[K4 + j] = f2bf_bits(pr[j]);
+      b += (double)pr[j] * bff2[j];
+    }
+    for (int k = 5 * C; k < ldp; ++k) row[k] = 0;
+    bias[n] = (float)b;
+  }
+}
 
 }  // namespace tair
 
@@ -503,6 +569,14 @@ void build_st(tair_cldm* h, STW& s, const std::string& pfx, int C, int lvl) {
   s.poutb = vec_alloc(h, C);
   add_vec(h, pfx + ".proj_out.bias", C, s.poutb);
   s.kvcache = (bf16*)dmalloc(h, (size_t)h->cfg.max_batch * h->cfg.context_len * 2 * C * sizeof(bf16));
+  s.tb = tb;
+  s.pfx = pfx;
+#ifndef TAIR_NO_FFPOUT  // (A/B variant builds only: the two-launch FF-out + proj_out at every shape)
+  alloc_w(h, s.fpo, C, 4 * C, C);
+  s.fpob = vec_alloc(h, C);
+  h->by_key[tb + ".ff.net.2.weight"]->keep_src = true;
+  h->by_key[pfx + ".proj_out.weight"]->keep_src = true;
+#endif
   if (f8_ops(h) & F8_PROJ_IN) alloc_w8_gn(h, s.pin, s.gn, C, false);  // proj_in: on the GroupNorm's e4m3 output
   if (f8_ops(h) & F8_LN_LINEAR) {  // the LayerNorm-fed linears run e4m3 x e4m3
     alloc_w8(h, s.qkv);
@@ -510,7 +584,6 @@ void build_st(tair_cldm* h, STW& s, const std::string& pfx, int C, int lvl) {
     alloc_w8(h, s.ff1);
   } else if (h->ln_fold) {  // bf16: the LayerNorms fold into their consumers
     s.fold = true;
-    s.tb = tb;
     s.fb_qkv = vec_alloc(h, 3 * C);
     s.cs_qkv = vec_alloc(h, 3 * C);
     s.fb_q2 = vec_alloc(h, C);
@@ -783,7 +856,7 @@ hipError_t run_gemm(tair_cldm* h, GemmArgs* a, const Fwd& f, double f8_kfrac = 1
   double alg = 0.0;
   if (h->prof) {
     int bm = 0, bn = 0, sp = 0, kern = 0;
-    gemm_plan_query(a[0], &bm, &bn, &sp, &kern);  // the plan gemm_grouped launches
+    gemm_plan_query(a[0], &bm, &bn, &sp, &kern, f.n);  // the plan gemm_grouped launches
     char buf[200];
     snprintf(buf, sizeof(buf), "gemm mode=%d M=%d N=%d K=%d Kx=%d tile=%dx%d splits=%d kern=%d group=%d", a[0].amode,
              a[0].M, a[0].N, (int)kreal, a[0].Kx, bm, bn, sp, kern, f.n);
@@ -1125,6 +1198,13 @@ hipError_t resblock(tair_cldm* h, const Fwd& f, const ResW* const* r, const bf16
   return run_gemm(h, a, f, f8b ? 9.0 * cout / r[0]->c2.ld8 : 1.0);
 }
 
+// FF-out composed with proj_out, selected per launch by the images in it (M / rows per image): the
+// one- and two-image steps (B = 1, the guided B = 2) are chains of latency-bound launches on 64-row split-K tiles, where
+// a launch less is what pays; batched steps keep the two launches, FF-out on the 128x320 register-staged plans and
+// proj_out on the 2-stage 64x64 tiles that the composite's K = 5C would leave
+constexpr int FFPOUT_MAX_IMAGES = 2;
+bool ffpout_composed(int images) { return images <= FFPOUT_MAX_IMAGES; }
+
 // SpatialTransformer.forward (attention.py:334-353) + BasicTransformerBlock (:265-274), in place on x[i]
 hipError_t transformer(tair_cldm* h, const Fwd& f, const STW* const* st, bf16* const* x, const int* ldx,
                        double* const* xst, const Tg* otg, int lvl) {
@@ -1278,19 +1358,33 @@ hipError_t transformer(tair_cldm* h, const Fwd& f, const STW* const* st, bf16* c
     a[i].ldo = 4 * C;
   }
   TRY(run_gemm(h, a, f, kf));
-  for (int i = 0; i < n; ++i) {
-    a[i] = dense(f.l[i].w->F, 4 * C, M, st[i]->ff2);
-    a[i].bias = V(h, st[i]->ff2b);
-    a[i].res = X0[i];
-    a[i].ld_res = C;
-    a[i].out = X0[i];
-    a[i].ldo = C;
+  // FF-out and proj_out are a linear map of a linear map: where ffpout_composed() selects it, one GEMM over
+  // [F | X2] against [Wpout Wff2 | Wpout] (STW::fpo, K = 4C + the K-extension C) with proj_out's epilogue
+  bool composed = ffpout_composed(f.B);
+  for (int i = 0; i < n; ++i) composed = composed && st[i]->fpo.p;
+  if (!composed) {
+    for (int i = 0; i < n; ++i) {
+      a[i] = dense(f.l[i].w->F, 4 * C, M, st[i]->ff2);
+      a[i].bias = V(h, st[i]->ff2b);
+      a[i].res = X0[i];
+      a[i].ld_res = C;
+      a[i].out = X0[i];
+      a[i].ldo = C;
+    }
+    TRY(run_gemm(h, a, f));
   }
-  TRY(run_gemm(h, a, f));
   // proj_out + residual (in place on x)
   for (int i = 0; i < n; ++i) {
-    a[i] = dense(X0[i], C, M, st[i]->pout);
-    a[i].bias = V(h, st[i]->poutb);
+    if (composed) {
+      a[i] = dense(f.l[i].w->F, 4 * C, M, st[i]->fpo);
+      a[i].X = X0[i];
+      a[i].ldx = C;
+      a[i].Kx = C;
+      a[i].bias = V(h, st[i]->fpob);
+    } else {
+      a[i] = dense(X0[i], C, M, st[i]->pout);
+      a[i].bias = V(h, st[i]->poutb);
+    }
     a[i].res = x[i];
     a[i].ld_res = ldx[i];
     a[i].res_lo = lo_of(h, x[i]);
@@ -2223,6 +2317,34 @@ int fold_st(tair_cldm* h, STW& st, std::vector<float>& ar) {
   return TAIR_OK;
 }
 
+// FF-out composed with proj_out of one transformer (STW::fpo, compose_ffpout).  The composite has no backing
+// parameter: it is rebuilt when ff.net.2 or proj_out (weight or bias) was loaded since the last finalize, else its
+// bias slot is carried over from the last finalized arena (the packed weight stays on the device).  The fp32 rows
+// of both weights stay on the host so either can be loaded again alone (20 C^2 bytes per transformer).
+int compose_st(tair_cldm* h, STW& st, std::vector<float>& ar) {
+  if (!st.fpo.p) return TAIR_OK;
+  const int C = st.C;
+  ParamDst* pf = h->by_key[st.tb + ".ff.net.2.weight"];
+  ParamDst* pfb = h->by_key[st.tb + ".ff.net.2.bias"];
+  ParamDst* pp = h->by_key[st.pfx + ".proj_out.weight"];
+  ParamDst* ppb = h->by_key[st.pfx + ".proj_out.bias"];
+  if (!pf->dirty && !pfb->dirty && !pp->dirty && !ppb->dirty) {
+    for (int n = 0; n < C; ++n) ar[st.fpob + n] = h->arena_host[st.fpob + n];
+    return TAIR_OK;
+  }
+  if (pf->w_src.size() != (size_t)4 * C * C || pp->w_src.size() != (size_t)C * C) {
+    set_error("finalize: no fp32 rows of '%s' / '%s' to compose", pf->key.c_str(), pp->key.c_str());
+    return TAIR_ERR_STATE;
+  }
+  const Weight& w = st.fpo;
+  std::vector<uint16_t> packed((size_t)C * w.ldw);
+  compose_ffpout(pp->w_src.data(), pf->w_src.data(), pfb->vec_src.data(), ppb->vec_src.data(), C, packed.data(),
+                 w.ldw, &ar[st.fpob]);
+  hipError_t e = hipMemcpy(w.p, packed.data(), packed.size() * 2, hipMemcpyHostToDevice);
+  if (e != hipSuccess) return fail_hip(e);
+  return TAIR_OK;
+}
+
 int tair_cldm_finalize(tair_cldm* h) {
   tair::g_err[0] = 0;
   if (!h) return TAIR_ERR_ARG;
@@ -2248,6 +2370,11 @@ int tair_cldm_finalize(tair_cldm* h) {
     if (rc == TAIR_OK) rc = fold_st(h, net->midst, ar);
     for (auto& d : net->dec)
       if (rc == TAIR_OK && d.has_st) rc = fold_st(h, d.st, ar);
+    for (auto& b : net->enc)
+      if (rc == TAIR_OK && b.has_st) rc = compose_st(h, b.st, ar);
+    if (rc == TAIR_OK) rc = compose_st(h, net->midst, ar);
+    for (auto& d : net->dec)
+      if (rc == TAIR_OK && d.has_st) rc = compose_st(h, d.st, ar);
     if (rc != TAIR_OK) return rc;
   }
   // GroupNorm-fed fp8 consumers: static per-channel activation scales from the GroupNorm's gamma / beta

@@ -219,7 +219,7 @@ bool halo_tile_built(int W, int bm, int bn) {
   return (W == 32 || W == 16) && (bn == 128 || bn == 160 || bn == 192);
 }
 
-void gemm_plan(const GemmArgs& a, int* bm, int* bn, int* splits, int* kern) {
+void gemm_plan(const GemmArgs& a, int* bm, int* bn, int* splits, int* kern, int lanes) {
   const int ktiles = (a.K + a.Kx) / BK;
   const bool conv = a.amode != A_DENSE;
   *splits = 1;
@@ -269,6 +269,40 @@ void gemm_plan(const GemmArgs& a, int* bm, int* bn, int* splits, int* kern) {
     int s = (int)((240 + tiles / 2) / tiles);
     if (s > ktiles / 2) s = ktiles / 2;
     if (s > 16) s = 16;
+    *splits = s < 1 ? 1 : s;
+    return;
+  }
+  // FF-out composed with proj_out (a dense GEMM with a K-extension: N = C, K = 4C, Kx = C; the one- and two-image
+  // steps only, cldm.cpp ffpout_composed): 64-row tiles, whose K slices combine in-kernel under proj_out's epilogue
+  // (residual and output hi + lo planes, GroupNorm statistics).  A slice takes cdiv(K-tiles, slices) tiles, so the
+  // K / Kx boundary may fall inside a slice.
+  // * one lane (the UNet decoder), swept at B = 1 and 2 with cold operands (profiles/ffpout_sweep.log): 128-column
+  //   tiles once 64x64 tiles outnumber the 256 CUs (B = 2, 64^2 / 32^2: 32.5 / 30.9 -> 28.7 / 27.9 us); slices while
+  //   the grid stays within one round of CUs and a slice keeps >= 10 K-tiles, or within the 512 workgroups the
+  //   cooperative combine holds resident and a slice keeps >= 16 (B = 1: 32^2 2 -> 3 slices 22.0 -> 20.0 us, 16^2
+  //   3 -> 6 slices 23.5 -> 21.4; 64^2 stays unsplit, 2 slices 20.9 -> 24.4; 8^2 10 slices 13.7)
+  // * two lanes in one launch (UNet + ControlNet encoder and middle): the rule of the other B = 1 linears below
+  //   (~200 workgroups per lane, >= 2.5 K-tiles per slice, >= 2 slices for a long K below a round of CUs), which
+  //   keeps the grouped grid within what the cooperative combine takes
+  if (!conv && a.Kx > 0) {
+    long tiles = (long)cdiv(a.M, 64) * cdiv(a.N, 64);
+    int s;
+    *bm = 64;
+    *bn = 64;
+    if (lanes <= 1) {
+      if (tiles > 256) {
+        *bn = 128;
+        tiles = (long)cdiv(a.M, 64) * cdiv(a.N, 128);
+      }
+      s = 1;
+      for (int c = 2; c <= 16; ++c)
+        if ((tiles * c <= 256 && ktiles / c >= 10) || (tiles * c <= 512 && ktiles / c >= 16)) s = c;
+    } else {
+      s = (int)((200 + tiles / 2) / tiles);
+      if (s < 2 && ktiles >= 32 && tiles < 256) s = 2;
+      if (s > (2 * ktiles) / 5) s = (2 * ktiles) / 5;
+      if (s > 16) s = 16;
+    }
     *splits = s < 1 ? 1 : s;
     return;
   }
@@ -425,9 +459,12 @@ bool gemm_gn_ok(const GemmArgs& a) {
   return e == hipSuccess;
 }
 
-hipError_t gemm_plan_query(const GemmArgs& a, int* bm, int* bn, int* splits, int* kern) {
+hipError_t gemm_plan_query(const GemmArgs& a, int* bm, int* bn, int* splits, int* kern, int lanes) {
+  GemmArgs g[MAX_GROUP];  // grouped GEMMs share the shape: the plan of `lanes` copies
+  const int n = lanes < 1 ? 1 : lanes > MAX_GROUP ? MAX_GROUP : lanes;
+  for (int i = 0; i < n; ++i) g[i] = a;
   g_gemm_dry = true;
-  const hipError_t e = gemm_grouped(&a, 1, nullptr);
+  const hipError_t e = gemm_grouped(g, n, nullptr);
   g_gemm_dry = false;
   *bm = g_dry_plan[0];
   *bn = g_dry_plan[1];
@@ -507,7 +544,7 @@ hipError_t gemm_grouped(const GemmArgs* args, int n, hipStream_t s) {
       return hipErrorInvalidValue;
     }
   int bm, bn, splits, kern;
-  gemm_plan(a, &bm, &bn, &splits, &kern);
+  gemm_plan(a, &bm, &bn, &splits, &kern, n);
   if (a.force_bm) bm = a.force_bm;
   if (a.force_bn) bn = a.force_bn;
   if (a.force_splits) splits = a.force_splits;

@@ -58,6 +58,13 @@ int tair_fault_count(int reset, int* count) {
 
 int tair_k_gemm_desc_bytes(void) { return (int)sizeof(tair_gemm_desc); }
 
+int tair_k_compose_ffpout(const float* wpout, const float* wff2, const float* bff2, const float* bpout, int C,
+                          void* packed, int ldp, float* bias) {
+  if (!wpout || !wff2 || !bff2 || !bpout || !packed || !bias || C < 1 || ldp < 5 * C) return -1;
+  compose_ffpout(wpout, wff2, bff2, bpout, C, (uint16_t*)packed, ldp, bias);
+  return 0;
+}
+
 int tair_k_gemm_plan(const tair_gemm_desc* d, int* bm, int* bn, int* splits, int* kern) {
   if (!d || !bm || !bn || !splits || !kern) return -1;
   const GemmArgs a = gemm_args_of(d);

@@ -163,7 +163,7 @@ constexpr int ATTN_TICKETS = 16384;  // attention key-split tickets per scratch 
 hipError_t gemm_grouped(const GemmArgs* a, int n, hipStream_t s);  // n <= MAX_GROUP, same shapes
 bool gemm_gn_ok(const GemmArgs& a);  // a GroupNorm-on-load plan exists for a (validation only, no launch)
 // the plan gemm_grouped would launch for a (validation only, touches no device)
-hipError_t gemm_plan_query(const GemmArgs& a, int* bm, int* bn, int* splits, int* kern);
+hipError_t gemm_plan_query(const GemmArgs& a, int* bm, int* bn, int* splits, int* kern, int lanes = 1);
 hipError_t gemm_init();  // one-time kernel attribute setup (call outside stream capture)
 // Faults the GEMM kernels detected since the last call (a cooperative split-K slice that gave up waiting for
 // its tile's other slices and therefore summed incomplete slabs); reset = true clears the counter.  Host
@@ -181,7 +181,7 @@ constexpr int GEMM_KERN_HALO = 3;
 // keeps its number of rounds over the CUs); force_stages 100 + S forces depth S
 constexpr int GEMM_KERN_DEEP = 4;
 bool conv_halo_ok(const GemmArgs& a);
-void gemm_plan(const GemmArgs& a, int* bm, int* bn, int* splits, int* kern = nullptr);
+void gemm_plan(const GemmArgs& a, int* bm, int* bn, int* splits, int* kern = nullptr, int lanes = 1);
 size_t gemm_partial_elems(const GemmArgs& a);
 // whether a GEMM's plan can produce LayerNorm row statistics (GemmArgs.rst): tile kernels with at
 // most 128-row tiles (the statistics live in the epilogue's 2 KiB reduction area)
@@ -243,6 +243,13 @@ hipError_t quant_rows_fp8(const bf16* w, int rows, int K, int ldw, uint8_t* q, i
 // columns of a K-extension follow as bf16(w[r][K + j] / s[r]) at byte k8 + 2j (rows of ldq bytes)
 hipError_t quant_rows_fp8_ex(const bf16* w, int rows, int K, int Kx, int ldw, const float* a, uint8_t* q, int ldq,
                              int k8, float* scale, hipStream_t s);
+
+// FF-out composed with proj_out (host, cldm.cpp): out = x + [F | X2] . [Wpout Wff2 | Wpout]^T + (Wpout
+// b_ff2 + b_pout).  From the fp32 rows Wpout [C][C], Wff2 [C][4C]: packed [C][ldp >= 5C] bf16 bits (columns past 5C
+// zeroed), the product accumulated in fp32 over blocks of 64 terms and across blocks in fp64, rounded once; bias [C]
+// from an fp64 sum.  Blocked over rows and columns, on up to 16 threads when the product is large.
+void compose_ffpout(const float* wpout, const float* wff2, const float* bff2, const float* bpout, int C,
+                    uint16_t* packed, int ldp, float* bias);
 
 // ---- attention ---------------------------------------------------------------------------
 // O[b, i, h*64:(h+1)*64] = softmax(Q K^T * scale) V for every (b, h); d = 64.

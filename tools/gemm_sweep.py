@@ -36,6 +36,10 @@ SHAPES = {
     "conv32in": (1, 32, 640, 320, 0), "conv16in": (1, 16, 1280, 640, 0), "up32": (3, 32, 1280, 1280, 0),
     "up16": (3, 16, 1280, 1280, 0), "down16": (2, 16, 640, 640, 0), "down8": (2, 8, 1280, 1280, 0),
     "lin64ff1plain": (0, 64, 2560, 320, 0), "lin32ff1plain": (0, 32, 5120, 640, 0),  # (no GEGLU epilogue)
+    # FF-out composed with proj_out: N = C, K = 4C over F + the K-extension C over the stream;
+    # the two launches it replaces are lin*ff2 + lin*proj
+    "lin64ffpo": (0, 64, 320, 1280, 320), "lin32ffpo": (0, 32, 640, 2560, 640), "lin16ffpo": (0, 16, 1280, 5120, 1280),
+    "lin8ffpo": (0, 8, 1280, 5120, 1280), "lin8ff2": (0, 8, 1280, 5120, 0),
 }
 HALO_TILES = [(256, 64), (256, 128), (256, 160)]  # conv_halo_kernel (force_stages 9): stride-1 3x3, no Kx
 HALO_SPLITS = [1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 20]
@@ -116,6 +120,8 @@ def main():
     ap.add_argument("--sweep", action="store_true")
     ap.add_argument("--reps", type=int, default=20)
     ap.add_argument("--tiles", default="", help="restrict the sweep to these tiles, e.g. 64x64,128x320")
+    ap.add_argument("--splits", default="", help="split counts of the sweep, e.g. 1,2,4,5,10 (default 1,2,3,4,6,8)")
+    ap.add_argument("--all", action="store_true", help="(--sweep) also print every candidate's time, not only the best")
     a = ap.parse_args()
     L = _lib.lib()
     stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
@@ -137,17 +143,22 @@ def main():
             best = (t_plan, "plan")
             if a.sweep:
                 tiles = [tuple(int(v) for v in t.split("x")) for t in a.tiles.split(",")] if a.tiles else TILES
+                splits = [int(v) for v in a.splits.split(",")] if a.splits else SPLITS
+                cand = {}
                 for bm, bn in tiles:
                     if bn > 128 and (r.M * N) / (abs(bm) * bn) < 64:
                         continue
-                    for s in SPLITS:
+                    for s in splits:
                         if s > (r.Kt + Kx) // 64 // 2 and s > 1:
                             continue
                         for sem in ([False, True] if s > 1 else [False]):
                             ds = [r.desc(i, bm, bn, s, sem) for i in range(len(r.sets))]
                             t = time_fn(lambda i: run(ds[i % len(ds)]), a.reps)
+                            cand[f"{bm}x{bn}/s{s}{'/sem' if sem else ''}"] = round(t, 2)
                             if t < best[0]:
                                 best = (t, f"{bm}x{bn}/s{s}{'/sem' if sem else ''}")
+                if a.all:
+                    print(json.dumps(dict(B=B, shape=nm, candidates_us=cand)), flush=True)
                 if mode == 1 and not Kx and side in (16, 32, 64) and (r.M % 256) == 0:
                     for bm, bn in HALO_TILES:
                         if bn == 64 and side != 64:
