@@ -33,7 +33,8 @@ typedef struct {
   void* out; int ldo; int out_f32;
   float* partial; int64_t partial_cap; /* split-K workspace (fp32 elements) or NULL */
   int force_bm, force_bn, force_splits;  /* 0 = heuristic */
-  int force_stages;                      /* 4: the 4-phase 256-row kernel; 2: 2-stage 64-row dense tiles */
+  int force_stages;                      /* 4: the 4-phase 256-row kernel; 2: 2-stage 64-row dense tiles;
+                                            100 + S: S-deep 64-row ring; 203: two-K-group 64-row tiles */
   int* tile_sem; int sem_cap;            /* split-K tickets (zeroed ints, one per output tile) or NULL:
                                             the last K-slice reduces in-kernel, else a reduce kernel */
   /* split-precision operands (the fp32-accurate VAE decoder): out_split 1 writes hi/lo/hi, 2 hi/hi/lo
@@ -85,9 +86,17 @@ int tair_fault_count(int reset, int* count);
 /* sizeof(tair_gemm_desc) as compiled into the library (bindings check their struct mirror against it). */
 int tair_k_gemm_desc_bytes(void);
 /* The plan tair_k_gemm would launch for d, without launching (host only, no device needed): tile bm x bn
- * (bm < 0: the BK = 32 ring tiles), K splits, kernel (0 tile, 1 4-phase, 2 2-stage shallow, 3 halo conv).
+ * (bm < 0: the BK = 32 ring tiles), K splits, kernel (0 tile, 1 4-phase, 2 2-stage shallow, 3 halo conv, 4 deep ring,
+ * 5 two-K-group 64-row tile).
  * Returns the validation status tair_k_gemm would report. */
 int tair_k_gemm_plan(const tair_gemm_desc* d, int* bm, int* bn, int* splits, int* kern);
+/* The two-K-group 64-row tiles (kernel 5; force_stages 203 forces them): loop trips of both K-groups over the
+ * workgroup's K-tile slice [kt0, kt1), and the K-tile group g (0 | 1) takes on a trip (a tile >= kt1: no MFMAs). */
+int tair_k_kgroup_trips(int kt0, int kt1);
+/* Tests only (process-wide): on != 0 makes every planned 3-stage 64-row tile plan the two-K-group kernel is built for
+ * take it, with half the K slices.  Returns the number of two-K-group launches since the previous call. */
+int tair_k_gemm_kgroup_force(int on);
+int tair_k_kgroup_tile(int kt0, int g, int trip);
 /* The plan tair_k_attention would launch (host only, no device needed): queries per wave / 16 (qsets),
  * key splits and keys per split, for a workspace of ws_bytes (< 0: unbounded). 0 on success. */
 int tair_k_attention_plan(int B, int H, int Sq, int Skv, int64_t ws_bytes, int* qsets, int* splits, int* kv_split);

@@ -140,6 +140,9 @@ SIGNATURES = {
     "tair_fault_count": (_I, [_I, ctypes.POINTER(_I)]),
     "tair_k_gemm_plan": (_I, [ctypes.POINTER(GemmDesc), ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I),
                               ctypes.POINTER(_I)]),
+    "tair_k_kgroup_trips": (_I, [_I, _I]),
+    "tair_k_gemm_kgroup_force": (_I, [_I]),
+    "tair_k_kgroup_tile": (_I, [_I, _I, _I]),
     "tair_k_attention_plan": (_I, [_I, _I, _I, _I, ctypes.c_int64, ctypes.POINTER(_I), ctypes.POINTER(_I),
                                    ctypes.POINTER(_I)]),
     "tair_k_attention": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, ctypes.c_float, _P]),

@@ -143,6 +143,8 @@ hipError_t gemm_init() {
   TAIR_HIP_CHECK((gemm_set_attrs<A_CONV3, SET_HALO>()));
   TAIR_HIP_CHECK((gemm_set_attrs<A_DENSE, SET_DEEP>()));
   TAIR_HIP_CHECK((gemm_set_attrs<A_CONV3, SET_DEEP>()));
+  TAIR_HIP_CHECK((gemm_set_attrs<A_DENSE, SET_KGROUP>()));
+  TAIR_HIP_CHECK((gemm_set_attrs<A_CONV3, SET_KGROUP>()));
   done = true;
   return hipSuccess;
 }
@@ -154,6 +156,9 @@ hipError_t launch_set(int amode, GemmGroup& P, int n, int bm, int bn, int splits
   if (kern == GEMM_KERN_DEEP)
     return amode == A_DENSE ? gemm_set_launch<A_DENSE, SET_DEEP>(P, n, bm, bn, splits, s)
                             : gemm_set_launch<A_CONV3, SET_DEEP>(P, n, bm, bn, splits, s);
+  if (kern == GEMM_KERN_KGROUP)
+    return amode == A_DENSE ? gemm_set_launch<A_DENSE, SET_KGROUP>(P, n, bm, bn, splits, s)
+                            : gemm_set_launch<A_CONV3, SET_KGROUP>(P, n, bm, bn, splits, s);
   if (kern == GEMM_KERN_PHASE) {
     switch (amode) {
       case A_DENSE: return gemm_set_launch<A_DENSE, SET_PHASE>(P, n, bm, bn, splits, s);
@@ -421,6 +426,18 @@ size_t gemm_partial_elems(const GemmArgs& a) {
 static bool g_skip_reduce = false;  // TAIR_ABLATE bit 8 (timing experiments only)
 void gemm_set_skip_reduce(bool on) { g_skip_reduce = on; }
 
+// Tests only (host, process-wide; tests/test_kgroup_gpu.py): every planned 3-stage 64-row tile plan the two-K-group
+// kernel is built for (bf16 dense / stride-1 conv, no GroupNorm on load) takes it, with half the K slices, so a
+// whole model forward runs on it.  Returns the two-K-group launches since the last call.
+static bool g_kgroup_force = false;
+static long g_kgroup_launches = 0;
+long gemm_set_kgroup_force(bool on) {
+  g_kgroup_force = on;
+  const long c = g_kgroup_launches;
+  g_kgroup_launches = 0;
+  return c;
+}
+
 // Largest split count combined in-kernel (splitk_combine); larger splits use splitk_reduce_kernel.
 // TAIR_INK_SMAX overrides (A/B experiments; 0 or 1 = never in-kernel).
 static int ink_smax() {
@@ -446,6 +463,29 @@ size_t plan_lds(int kern, int bm, int bn, int W, bool halo_s2) {
   }
   const int st = kern == GEMM_KERN_SHALLOW ? 2 : (bm == 128 && bn == 320) || (bm == 256 && bn >= 256) ? 2 : 3;
   return (size_t)st * (bm + bn) * 128;
+}
+// The K-slice count of the two-K-group form of a planned 3-stage 64-row tile plan (bm x bn, `splits` slices, `lanes`
+// grouped GEMMs), or 0 to keep the 4-wave plan.  From the per-shape sweep at B = 1 (profiles/kgroup_sweep.log,
+// DESIGN.md §2.1): stride-1 3x3 convs of ONE image (a.Bn == 1: the only grids swept; the two-image step keeps its
+// plans) whose whole grid is one round of the 256 CUs, with as many slices as that round holds -- at most the 4-wave
+// plan's count, a slice keeping >= 15 K-tiles (conv32 5 -> 3 slices, conv16 and conv16in 10 -> 6, conv64 2 -> 1).
+// Not taken: the linears (8-20% faster in isolation, but their kernel class did not get faster in the step:
+// DESIGN.md §2.1), grids of more than 512 workgroups, plans without split-K tickets (their slices go through the
+// reduce kernel: not swept), the 8x8 level's < 32-tile grids (conv8: no plan of the planned tile beat the 4-wave
+// one), and grids of more than 256 tiles.
+int kgroup_rule(const GemmArgs& a, int bm, int bn, int splits, int lanes) {
+  const int ktiles = (a.K + a.Kx) / BK;
+  const long tiles = (long)cdiv(a.M, bm) * cdiv(a.N, bn) * lanes;
+  if (a.amode != A_CONV3 || a.Bn != 1 || !a.tile_sem) return 0;
+  if (tiles * splits > 512 || tiles > 256 || tiles < 32) return 0;
+  int s2 = std::min((int)(256 / tiles), ktiles / 15);
+  s2 = std::max(1, std::min(s2, splits));
+  while (s2 > 1 && (long)(s2 - 1) * cdiv(ktiles, s2) >= ktiles) --s2;  // (no empty K slice)
+  if (ktiles / s2 < 4) return 0;  // each K-group keeps >= 2 K-tiles
+  // one slice in place of a split plan only up to 100 K-tiles: the one longer shape swept, conv64 over 960 channels
+  // (135 K-tiles), ran 59.0 us against the 4-wave plan's 61.8 / 59.4, inside that plan's own spread
+  if (s2 == 1 && splits > 1 && ktiles > 100) return 0;
+  return s2;
 }
 bool deep_built(int bm, int bn, int st) {
   return bm == 64 && ((bn == 64 && (st == 4 || st == 5 || st == 6 || st == 8)) || (bn == 128 && st >= 4 && st <= 6));
@@ -554,7 +594,8 @@ hipError_t gemm_grouped(const GemmArgs* args, int n, hipStream_t s) {
   }
   int tile_stages = 0;
   if (a.force_bm || a.force_stages)
-    kern = a.force_stages >= 100 ? GEMM_KERN_DEEP
+    kern = a.force_stages >= 200 ? GEMM_KERN_KGROUP
+           : a.force_stages >= 100 ? GEMM_KERN_DEEP
            : a.force_stages == 9 ? GEMM_KERN_HALO
            : a.force_stages >= 4 ? GEMM_KERN_PHASE : a.force_stages == 2 ? GEMM_KERN_SHALLOW : GEMM_KERN_TILE;
   if (kern == GEMM_KERN_DEEP) {
@@ -564,6 +605,12 @@ hipError_t gemm_grouped(const GemmArgs* args, int n, hipStream_t s) {
                 tile_stages);
       return hipErrorInvalidValue;
     }
+  }
+  if (kern == GEMM_KERN_KGROUP &&
+      (a.f8 || a.gn_st || !gemm_kgroup_built(a.amode, bm, bn, a.force_stages - 200))) {
+    set_error("gemm: two-K-group tile %dx%d with %d stages not built (bf16 dense / stride-1 conv, 64x64 / 64x128, "
+              "3 stages, no GroupNorm on load; mode %d, fp8 %d)", bm, bn, a.force_stages - 200, a.amode, a.f8);
+    return hipErrorInvalidValue;
   }
   if (kern == GEMM_KERN_HALO && (!conv_halo_ok(a) || !halo_tile_built(a.W, bm, bn))) {
     set_error("gemm: halo tiles take bf16 stride-1 3x3 convs over 16/32/64-wide images, tile %dx%d not built "
@@ -666,6 +713,25 @@ hipError_t gemm_grouped(const GemmArgs* args, int n, hipStream_t s) {
     const int units = kern == GEMM_KERN_HALO ? a.C / 64 : (a.K + a.Kx) / (bm < 0 ? 32 : BK);
     while (splits > 1 && (long)(splits - 1) * cdiv(units, splits) >= units) --splits;
   }
+  // B = 1 grids: the two-K-group form of the 3-stage 64-row tiles (gemm_kern.h gemm_kgroup_kernel) with half the K
+  // slices, where that keeps the grid within one workgroup per CU and gives each K-group >= 2 K-tiles; the shapes
+  // come from the per-shape sweep (kgroup_rule above).  Batched grids (> 512 workgroups) never reach it.
+  // -DTAIR_NO_KGROUP (build.variant_lib, paired A/B) compiles the rule out.
+#ifndef TAIR_NO_KGROUP
+  if (kern == GEMM_KERN_TILE && !a.force_bm && !a.force_bn && !a.force_splits && !a.force_stages && !a.f8 &&
+      !a.gn_st && gemm_kgroup_built(a.amode, bm, bn, 3)) {
+    int s2 = kgroup_rule(a, bm, bn, splits, n);
+    if (g_kgroup_force) {
+      const int units = (a.K + a.Kx) / BK;
+      s2 = cdiv(splits, 2);
+      while (s2 > 1 && (long)(s2 - 1) * cdiv(units, s2) >= units) --s2;
+    }
+    if (s2) {
+      kern = GEMM_KERN_KGROUP;
+      splits = s2;
+    }
+  }
+#endif
   // B = 1 grids (TAIR_B1_DEEP, A/B experiment): the 64-row tiles take the deepest ring that keeps the grid's
   // number of rounds over the 256 CUs (workgroups per CU limited by the LDS), at most one stage beyond the
   // slice's K-tiles
@@ -688,12 +754,12 @@ hipError_t gemm_grouped(const GemmArgs* args, int n, hipStream_t s) {
   // at once (2 workgroups per CU at most: a tile's slices then wait only for resident or next-dispatched
   // workgroups); TAIR_COOP=0 turns it off (A/B experiments: the last-arriver combine / reduce kernel)
   static const bool coop_env = [] { const char* e = getenv("TAIR_COOP"); return !e || atoi(e) != 0; }();
-  const bool coop_kind = coop_env && !g_skip_reduce && kern == GEMM_KERN_TILE && bm == 64 &&
+  const bool coop_kind = coop_env && !g_skip_reduce && (kern == GEMM_KERN_TILE || kern == GEMM_KERN_KGROUP) && bm == 64 &&
                          a.amode != A_CONV3_SMALLC && !(a.probe & 4);
   // LayerNorm row statistics come from the one epilogue that sees final values: K slices must combine
   // in-kernel (64-row tile kernels: cooperatively, or at most ink_smax() slices), else K is not split
   if (a.rst && splits > 1)
-    splits = ((kern == GEMM_KERN_TILE || kern == GEMM_KERN_DEEP) && bm == 64 && a.tile_sem)
+    splits = ((kern == GEMM_KERN_TILE || kern == GEMM_KERN_DEEP || kern == GEMM_KERN_KGROUP) && bm == 64 && a.tile_sem)
                  ? (coop_kind ? splits : std::min(splits, std::max(1, ink_smax()))) : 1;
   if (a.amode < A_DENSE || a.amode > A_CONV3_SMALLC) {
     set_error("gemm: bad amode %d", a.amode);
@@ -718,13 +784,15 @@ hipError_t gemm_grouped(const GemmArgs* args, int n, hipStream_t s) {
   // (the launcher re-checks the grid against the device's CU count x the chosen kernel's occupancy and falls back
   // to the last-arriver combine when the grid is not resident at once; 512 = the 256-CU part at 2 per CU bounds
   // the plans that ask)
-  bool coop = splits > 1 && coop_kind && grid_wgs <= 2L * 256;
+  // (the two-K-group tiles hold a CU each: 256)
+  bool coop = splits > 1 && coop_kind && grid_wgs <= (kern == GEMM_KERN_KGROUP ? 256 : 2L * 256);
   for (int i = 0; i < n && coop; ++i)
     coop = args[i].tile_sem && tiles_all <= args[i].sem_cap &&
            (size_t)tiles_all * splits * abm * bn <= args[i].partial_cap;
   bool ink = splits > 1 && (coop || splits <= ink_smax() || (a.probe & 4)) && !g_skip_reduce &&
-             a.amode != A_CONV3_SMALLC && (kern == GEMM_KERN_TILE || kern == GEMM_KERN_DEEP) &&
-             bm == 64;  // 4-wave 64-row tiles: <= 8 fragments per wave
+             a.amode != A_CONV3_SMALLC &&
+             (kern == GEMM_KERN_TILE || kern == GEMM_KERN_DEEP || kern == GEMM_KERN_KGROUP) &&
+             bm == 64;  // 4-wave 64-row tiles (and their two-K-group form): <= 8 fragments per wave
   for (int i = 0; i < n && ink; ++i)
     ink = args[i].tile_sem && tiles_all <= args[i].sem_cap &&
           (size_t)tiles_all * splits * abm * bn <= args[i].partial_cap;
@@ -822,6 +890,7 @@ hipError_t gemm_grouped(const GemmArgs* args, int n, hipStream_t s) {
     if (g_gn_halo_only && a.gn_st && kern != GEMM_KERN_HALO) return hipErrorNotSupported;
     return hipSuccess;
   }
+  if (kern == GEMM_KERN_KGROUP) ++g_kgroup_launches;
   hipError_t e = !a.f8 ? launch_set(a.amode, P, n, bm, bn, splits, kern, s)
                  : a.amode == A_DENSE ? launch_f8<A_DENSE>(P, n, bm, bn, splits, s, kern == GEMM_KERN_SHALLOW)
                                       : gemm_set_launch<A_CONV3, SET_F8>(P, n, bm, bn, splits, s);

@@ -1025,7 +1025,7 @@ TAIR_DEV void splitk_coop(const PA& p, f32x4 (&acc)[FN][FM], int m0, int n0, int
         done = v >= S || v <= t;
         if (!done) __builtin_amdgcn_s_sleep(2);
       }
-      int* fault = kernarg0<GemmGroup>().fault;  // (cooperative plans run only in gemm_tile_kernel)
+      int* fault = kernarg0<GemmGroup>().fault;  // (cooperative plans: gemm_tile_kernel / gemm_kgroup_kernel, both GemmGroup)
       if (!done && fault) __hip_atomic_fetch_add(fault, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
     }
   }
@@ -2039,6 +2039,184 @@ __global__ __launch_bounds__(WMW * WNW * 64, (tile_min_waves<BM, BN, STAGES>()))
 }
 
 // ---------------------------------------------------------------------------------------------
+// Two-K-group form of the 3-stage 64-row tiles (B = 1 grids; bf16, A_DENSE / A_CONV3).  512 threads: waves 0-3
+// are K-group 0, waves 4-7 K-group 1, each group with gemm_tile_kernel's 2 x 2 wave layout, fragments, DMA lane
+// mapping and its own 3-stage ring, so every SIMD holds two independent instruction streams for the whole loop
+// (the 4-wave tile's single wave per SIMD waits out its own issue chain: ~1000 cycles per K-tile for 256 cycles
+// of MFMA).  Inside the workgroup's K slice [kt0, kt1) group g takes K-tiles kt0 + g, kt0 + g + 2, ...; both
+// groups run kgroup_trips(kt0, kt1) loop trips with the same waits and barriers (the barrier spans all 8 waves),
+// and a group without a real tile on its last trip issues its clamped copies and skips only the MFMAs.  After the
+// loop group 1 hands its accumulator fragments over through the LDS (fragment-native, lane-linear 16-byte pieces:
+// 16 / 32 KiB of ring memory), group 0 forms own + other, group 1's waves end, and waves 0-3 run the 4-wave tile's
+// epilogue unchanged (NT = 256, the same LDS geometry: the same bits as the 4-wave tile at the same K order per
+// group).  Every barrier behind that point is a workgroup s_barrier, which counts only the waves still alive.
+// No GroupNorm on load, no fp8 (the launcher refuses both).
+template <int BM, int BN, int AMODE>
+__global__ __launch_bounds__(512) void gemm_kgroup_kernel(const GemmGroup P_arg) {
+  constexpr int WMW = 2, WNW = 2, NW = 4, STAGES = 3;
+  constexpr int WM = BM / WMW, WN = BN / WNW;
+  constexpr int FM = WM / 16, FN = WN / 16;
+  constexpr int NA = BM / (8 * NW), NB = BN / (8 * NW);  // DMA instructions per wave per K-tile
+  constexpr int G = NA + NB;
+  constexpr int STAGE_BYTES = (BM + BN) * BK * 2;
+  constexpr int RING = STAGES * STAGE_BYTES;
+  static_assert(BM == 64 && (BN == 64 || BN == 128), "two-K-group tiles: 64x64 / 64x128");
+  static_assert(2 * RING <= 160 * 1024 && NW * FM * FN * 1024 <= RING, "LDS");
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+
+  const GemmGroup& P = kernarg0<GemmGroup>();
+  int xcd = P.xcd, tiles_m = P.tiles_m;
+  TAIR_PIN_ASM("" : "+s"(xcd), "+s"(tiles_m));
+  int bxl, by, bz;
+  xcd_remap(bxl, by, bz, xcd);
+  const int grp = bxl / tiles_m;
+  const int bx = bxl - grp * tiles_m;
+  const GemmArgs& p = P.g[grp];
+  stamp(p, 0);
+  const MainArgs ma = main_args(p);
+
+  const int tid = threadIdx.x, lane = tid & 63;
+  const int wid8 = __builtin_amdgcn_readfirstlane(tid >> 6);
+  const int kg = wid8 >> 2, wid = wid8 & 3;  // K-group, wave inside it
+  const int wm = wid % WMW, wn = wid / WMW;
+  const int m0 = bx * BM, n0 = by * BN;
+  const int ktot = (ma.K + ma.Kx) / BK;
+  const int per = (ktot + ma.splits - 1) / ma.splits;
+  const int kt0 = bz * per;
+  const int kt1 = min(ktot, kt0 + per);
+  const int trips = kgroup_trips(kt0, kt1);  // workgroup-uniform: no wave leaves the loop early
+
+  const int drow = lane >> 3;
+  const int dchunk = (lane & 7) ^ drow;
+  RowInfo<AMODE> rows[NA];
+#pragma unroll
+  for (int i = 0; i < NA; ++i) rows[i] = row_info<AMODE>(ma, m0 + (i * NW + wid) * 8 + drow, dchunk);
+  const bf16* wrow[NB];
+#pragma unroll
+  for (int i = 0; i < NB; ++i) {
+    const int n = n0 + (i * NW + wid) * 8 + drow;
+    wrow[i] = n < ma.N ? ma.Wt + (size_t)n * ma.ldw + dchunk * 8 : nullptr;
+  }
+  const bf16* zp = (const bf16*)g_zero_page;
+  const ActArgs pa = act_args(ma);
+
+  f32x4 acc[FN][FM];
+#pragma unroll
+  for (int j = 0; j < FN; ++j)
+#pragma unroll
+    for (int i = 0; i < FM; ++i) acc[j][i] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  char* const ring = smem + kg * RING;  // this group's ring
+#define TAIR_KG_ISSUE(KT, STG)                                                                    \
+  do {                                                                                            \
+    const int k0_ = (KT) * BK;                                                                    \
+    char* sb_ = ring + (STG) * STAGE_BYTES;                                                       \
+    _Pragma("unroll") for (int i = 0; i < NA; ++i)                                                \
+      __builtin_amdgcn_global_load_lds((const void*)act_src<AMODE>(pa, rows[i], k0_),             \
+                                       TAIR_LDS(sb_ + (i * NW + wid) * 8 * 128), 16, 0, 0);       \
+    _Pragma("unroll") for (int i = 0; i < NB; ++i)                                                \
+      __builtin_amdgcn_global_load_lds((const void*)(wrow[i] ? wrow[i] + k0_ : zp),              \
+                                       TAIR_LDS(sb_ + BM * 128 + (i * NW + wid) * 8 * 128), 16, 0, 0); \
+  } while (0)
+
+  const uint32_t lds0 = lds_u32(ring);
+  const int ra = wm * WM + (lane & 15), rb = wn * WN + (lane & 15);
+  const uint32_t aoff0 = ra * 128 + ((((lane >> 4)) ^ (ra & 7)) << 4);
+  const uint32_t aoff1 = ra * 128 + (((4 + (lane >> 4)) ^ (ra & 7)) << 4);
+  const uint32_t boff0 = BM * 128 + rb * 128 + ((((lane >> 4)) ^ (rb & 7)) << 4);
+  const uint32_t boff1 = BM * 128 + rb * 128 + (((4 + (lane >> 4)) ^ (rb & 7)) << 4);
+
+  if (trips > 0) {
+    const int kl = kt1 - 1;
+#pragma unroll
+    for (int s = 0; s < STAGES - 1; ++s) TAIR_KG_ISSUE(min(kgroup_tile(kt0, kg, s), kl), s);
+    stamp(p, 1);
+    int stage = 0;
+    for (int j = 0; j < trips; ++j) {
+      const int t = kgroup_tile(kt0, kg, j);
+      wait_vmcnt<(STAGES - 2) * G>();  // this wave's copies of the trip's tile have landed
+      __builtin_amdgcn_s_barrier();    // ... and every wave's; the previous trip's buffer is free
+      if (j == 0) stamp(p, 2);
+      int ps = stage + STAGES - 1;
+      if (ps >= STAGES) ps -= STAGES;
+      TAIR_KG_ISSUE(min(kgroup_tile(kt0, kg, j + STAGES - 1), kl), ps);
+      if (t < kt1) {  // (wave-uniform; false only on group 1's last trip of an odd tile count)
+        const uint32_t sb = lds0 + stage * STAGE_BYTES;
+        bf16x8 xf[FM], wf[FN];
+        ds_read_frags<FM>(xf, sb + aoff0);
+        ds_read_frags<FN>(wf, sb + boff0);
+        wait_lgkmcnt<0>();
+        touch<FM>(xf);
+        touch<FN>(wf);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int jj = 0; jj < FN; ++jj)
+#pragma unroll
+          for (int i = 0; i < FM; ++i)
+            acc[jj][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[jj], xf[i], acc[jj][i], 0, 0, 0);
+        __builtin_amdgcn_sched_barrier(0);  // first-half MFMAs issue before the second half's reads
+        ds_read_frags<FM>(xf, sb + aoff1);
+        ds_read_frags<FN>(wf, sb + boff1);
+        wait_lgkmcnt<0>();
+        touch<FM>(xf);
+        touch<FN>(wf);
+        __builtin_amdgcn_sched_barrier(0);
+#pragma unroll
+        for (int jj = 0; jj < FN; ++jj)
+#pragma unroll
+          for (int i = 0; i < FM; ++i)
+            acc[jj][i] = __builtin_amdgcn_mfma_f32_16x16x32_bf16(wf[jj], xf[i], acc[jj][i], 0, 0, 0);
+      }
+      stage = (stage + 1 == STAGES) ? 0 : stage + 1;
+    }
+    wait_vmcnt<0>();  // drain the clamped tail copies: the rings are reused below
+    stamp(p, 3);
+  }
+#undef TAIR_KG_ISSUE
+
+  // combine: group 1 -> LDS (start of ring 0) -> group 0, own + other
+  __syncthreads();  // every wave's copies have landed and every wave is done reading the rings
+  if (kg == 1) {
+    static_for<0, FN>([&](auto J) {
+      constexpr int j = decltype(J)::value;
+      static_for<0, FM>([&](auto I) {
+        constexpr int i = decltype(I)::value;
+        *(f32x4*)(smem + (((wid * FN + j) * FM + i) * 64 + lane) * 16) = acc[j][i];
+      });
+    });
+  }
+  __syncthreads();
+  if (kg == 1) return;  // (wave-uniform) waves 4-7 are done
+  static_for<0, FN>([&](auto J) {
+    constexpr int j = decltype(J)::value;
+    static_for<0, FM>([&](auto I) {
+      constexpr int i = decltype(I)::value;
+      acc[j][i] = acc[j][i] + *(const f32x4*)(smem + (((wid * FN + j) * FM + i) * 64 + lane) * 16);
+    });
+  });
+
+  // waves 0-3: the 4-wave tile's epilogue (its first barrier follows the reads above)
+  {
+    const EpiArgs ep = epi_args(p);
+    switch (regstage_set<BM, BN, RING>(ep)) {
+#define TAIR_RS_CASE(S)                                                                 \
+      case (S): epilogue_regstage<(S), BM, BN, FM, FN, WM, WN, NW * 64, RING>(ep, acc, m0, n0, wm, wn, lane, smem); \
+        return;
+      TAIR_RS_CASE(E_BIAS | E_LNC | E_GEGLU)
+      TAIR_RS_CASE(E_BIAS | E_GEGLU)
+      TAIR_RS_CASE(E_BIAS | E_LNC)
+      TAIR_RS_CASE(E_BIAS)
+      TAIR_RS_CASE(E_BIAS | E_ROWST)
+      TAIR_RS_CASE(E_BIAS | E_RES | E_ROWST)
+      TAIR_RS_CASE(E_BIAS | E_RES)
+#undef TAIR_RS_CASE
+      default: break;
+    }
+  }
+  epilogue_tile<BM, BN, FM, FN, WM, WN, NW * 64, RING, true, true>(p, acc, m0, n0, wm, wn, lane, smem, bz);
+}
+
+// ---------------------------------------------------------------------------------------------
 // Halo-tile 3x3 convolution (stride 1, pad 1; unet.py:203-223 ResBlock convs), BM = 256 output pixels =
 // R = 256 / W whole image rows of one batch element (W in {16, 32, 64}), BN output channels, 8 waves
 // (4 m x 2 n, 64 x BN/2 each).  The implicit GEMM of gemm_tile_kernel streams one (64-channel chunk,
@@ -2826,6 +3004,34 @@ hipError_t launch_deep(GemmGroup& a, int n, int bm, int bn, int splits, hipStrea
   }
   return hipErrorInvalidValue;
 }
+// two-K-group 64-row tiles (gemm_kgroup_kernel): 8 waves, one 3-stage ring per group
+template <int BN, int AMODE>
+hipError_t launch_kgroup_tile(GemmGroup& a, int n, int splits, hipStream_t s) {
+  constexpr size_t LDS = 2 * T64x64::STAGES * (size_t)(64 + BN) * BK * sizeof(bf16);
+  a.tiles_m = cdiv(a.g[0].M, 64);
+  dim3 grid(a.tiles_m * n, cdiv(a.g[0].N, BN), splits);
+  if (a.g[0].coop) {  // as launch_tile: the cooperative combine only on grids the device holds at once
+    const long cap = resident_wgs(gemm_kgroup_kernel<64, BN, AMODE>, 512, LDS);
+    if ((long)grid.x * grid.y * grid.z > cap)
+      for (int i = 0; i < MAX_GROUP; ++i) a.g[i].coop = 0;
+  }
+  hipLaunchKernelGGL((gemm_kgroup_kernel<64, BN, AMODE>), grid, dim3(512), LDS, s, a);
+  return hipGetLastError();
+}
+template <int AMODE>
+hipError_t set_attrs_kgroup() {
+  TAIR_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_kgroup_kernel<64, 64, AMODE>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  TAIR_HIP_CHECK(hipFuncSetAttribute((const void*)gemm_kgroup_kernel<64, 128, AMODE>,
+                                     hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
+  return hipSuccess;
+}
+template <int AMODE>
+hipError_t launch_kgroup(GemmGroup& a, int n, int bm, int bn, int splits, hipStream_t s) {
+  if (bm == 64 && bn == 64) return launch_kgroup_tile<64, AMODE>(a, n, splits, s);
+  if (bm == 64 && bn == 128) return launch_kgroup_tile<128, AMODE>(a, n, splits, s);
+  return hipErrorInvalidValue;
+}
 template <int AMODE>
 hipError_t set_attrs_big() {
   TAIR_HIP_CHECK((set_attr_tile<T128x256, AMODE>()));
@@ -3058,7 +3264,7 @@ hipError_t launch_phase(GemmGroup& a, int n, int bm, int bn, int splits, hipStre
 template <int AMODE, int SET> hipError_t gemm_set_attrs();
 template <int AMODE, int SET> hipError_t gemm_set_launch(GemmGroup& a, int n, int bm, int bn, int splits, hipStream_t s);
 constexpr int SET_SMALL = 0, SET_BIG = 1, SET_REG = 2, SET_RING = 3, SET_PHASE = 4, SET_SHALLOW = 5, SET_F8 = 6,
-              SET_HALO = 7, SET_DEEP = 8;
+              SET_HALO = 7, SET_DEEP = 8, SET_KGROUP = 9;
 
 }  // namespace tair
 

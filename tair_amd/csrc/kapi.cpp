@@ -71,6 +71,10 @@ int tair_k_gemm_plan(const tair_gemm_desc* d, int* bm, int* bn, int* splits, int
   return gemm_plan_query(a, bm, bn, splits, kern) == hipSuccess ? 0 : -2;
 }
 
+int tair_k_gemm_kgroup_force(int on) { return (int)gemm_set_kgroup_force(on != 0); }
+int tair_k_kgroup_trips(int kt0, int kt1) { return kgroup_trips(kt0, kt1); }
+int tair_k_kgroup_tile(int kt0, int g, int trip) { return kgroup_tile(kt0, g, trip); }
+
 int tair_k_attention_plan(int B, int H, int Sq, int Skv, int64_t ws_bytes, int* qsets, int* splits, int* kv_split) {
   if (!qsets || !splits || !kv_split || B < 1 || H < 1 || Sq < 1 || Skv < 1) return -1;
   const AttnPlan p = attention_plan(B, H, Sq, Skv, ws_bytes < 0 ? (size_t)-1 : (size_t)ws_bytes);

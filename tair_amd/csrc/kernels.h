@@ -158,6 +158,8 @@ inline bool gemm_ring_built(int bm, int bn) {
 
 hipError_t gemm(const GemmArgs& a, hipStream_t s);
 void gemm_set_skip_reduce(bool on);  // timing-only ablation: no split-K reduce launches
+// tests only: every plan the two-K-group kernel is built for takes it (gemm.hip); returns its launches since the last call
+long gemm_set_kgroup_force(bool on);
 constexpr int GEMM_TICKETS = 16384;  // split-K tickets per scratch lane (tiles of one GEMM)
 constexpr int ATTN_TICKETS = 16384;  // attention key-split tickets per scratch lane (one 128-byte line per block)
 hipError_t gemm_grouped(const GemmArgs* a, int n, hipStream_t s);  // n <= MAX_GROUP, same shapes
@@ -180,6 +182,16 @@ constexpr int GEMM_KERN_HALO = 3;
 // DEEP: the 64-row tile kernel with a 4-8 deep LDS ring (B = 1 grids, gemm_grouped picks the depth so the grid
 // keeps its number of rounds over the CUs); force_stages 100 + S forces depth S
 constexpr int GEMM_KERN_DEEP = 4;
+// KGROUP: gemm_kgroup_kernel, the 3-stage 64x64 / 64x128 tile as 8 waves in two K-groups that share one output
+// tile (bf16 dense / stride-1 conv, no GroupNorm on load); force_stages 200 + 3 forces it
+constexpr int GEMM_KERN_KGROUP = 5;
+inline bool gemm_kgroup_built(int amode, int bm, int bn, int stages) {
+  return (amode == A_DENSE || amode == A_CONV3) && bm == 64 && (bn == 64 || bn == 128) && stages == 3;
+}
+// K-tiles of a two-K-group workgroup's slice [kt0, kt1): group g (0 | 1) takes kt0 + g, kt0 + g + 2, ...; both
+// groups run the same number of loop trips (a trip whose tile is >= kt1 skips the MFMAs only)
+__host__ __device__ inline int kgroup_trips(int kt0, int kt1) { return kt1 > kt0 ? (kt1 - kt0 + 1) / 2 : 0; }
+__host__ __device__ inline int kgroup_tile(int kt0, int g, int trip) { return kt0 + g + 2 * trip; }
 bool conv_halo_ok(const GemmArgs& a);
 void gemm_plan(const GemmArgs& a, int* bm, int* bn, int* splits, int* kern = nullptr, int lanes = 1);
 size_t gemm_partial_elems(const GemmArgs& a);

@@ -29,22 +29,28 @@ DEFAULT_VARIANTS = "plan,e1:plan,e2:plan,64x64/s1,64x64/s2/sem,64x128/s1,128x64/
 
 def parse_variant(v):
     """'[eP:][dS:]plan' | '[eP:][dS:]BMxBN/sS[/sem]' | '[eP:]haloBMxBN/sS' -> dict (eP: probe bits P, dS: deep
-    ring of S stages)"""
-    probe, deep = 0, 0
+    ring of S stages, k: the two-K-group 64-row tiles, t: the 4-wave tile kernel -- 't:plan' is the planner's plan
+    without the two-K-group rule)"""
+    probe, deep, stages = 0, 0, 0  # stages: GemmDesc.force_stages (0: the planner's kernel)
     while ":" in v:
         pre, v = v.split(":", 1)
         if pre.startswith("e"):
             probe = int(pre[1:])
         elif pre.startswith("d"):  # deep-ring tile kernel with this many stages
             deep = int(pre[1:])
+            stages = 100 + deep
+        elif pre == "k":  # the two-K-group 64-row tiles, 3-stage rings
+            stages = 203
+        elif pre == "t":  # the 4-wave tile kernel (with 'plan': tile and splits stay the planner's)
+            stages = 3
     if v == "plan":
-        return dict(probe=probe, bm=0, bn=0, s=0, sem=True, halo=False, deep=deep)
+        return dict(probe=probe, bm=0, bn=0, s=0, sem=True, halo=False, deep=deep, stages=stages)
     halo = v.startswith("halo")
     parts = v.replace("halo", "").split("/")
     bm, bn = (int(x) for x in parts[0].split("x"))
     s = int(parts[1][1:]) if len(parts) > 1 else 1
     sem = "sem" in parts
-    return dict(probe=probe, bm=bm, bn=bn, s=s, sem=sem, halo=halo, deep=deep)
+    return dict(probe=probe, bm=bm, bn=bn, s=s, sem=sem, halo=halo, deep=deep, stages=stages)
 
 
 def main():
@@ -69,7 +75,7 @@ def main():
         d0 = r.desc(0, 0, 0, 0, True)
         if L.tair_k_gemm_plan(ctypes.byref(d0), ctypes.byref(pb), ctypes.byref(pn), ctypes.byref(ps),
                               ctypes.byref(pk)) == 0:
-            row["plan"] = f"{pb.value}x{pn.value}/s{ps.value}/k{pk.value}"
+            row["planned"] = f"{pb.value}x{pn.value}/s{ps.value}/k{pk.value}"  # (the 'plan' variant's time: row["plan"])
         for vs in variants:
             v = parse_variant(vs)
             if v["halo"] and (mode != 1 or Kx or side not in (16, 32, 64)):
@@ -78,8 +84,8 @@ def main():
             for i in range(len(r.sets)):
                 d = r.desc(i, v["bm"], v["bn"], v["s"], v["sem"], v["halo"])
                 d.probe = v["probe"]
-                if v["deep"]:
-                    d.force_stages = 100 + v["deep"]
+                if v["stages"]:
+                    d.force_stages = v["stages"]
                 ds.append(d)
             try:
                 with torch.cuda.stream(s):

@@ -8,7 +8,8 @@ The variant is the same sources with one compile-time macro (no runtime switch i
 
 Each run is `bench.py` itself (default workload: B = 1, 512^2, 50 steps, VAE decode included; `--config 2` for the
 batched configs[2]) in a FRESH child process, the library selected by TAIR_LIB_VARIANT in the child's environment;
-the runs alternate (variant, product) for `--pairs` pairs on one box.  One JSON line per run goes to `--log`, then a
+the runs alternate (variant, product), the order swapped from pair to pair, for `--pairs` pairs on one box
+(`--variant NAME`: the same A/B against another baseline build, e.g. nokgroup = -DTAIR_NO_KGROUP).  One JSON line per run goes to `--log`, then a
 summary line: per-pair gain, median gain, and the spread (max - min) of the variant's own runs, the noise the gain has
 to clear.  `--finalize` instead times tair_cldm_finalize of the full-width model once per library (fresh children).
 
@@ -98,14 +99,18 @@ def main():
     ap.add_argument("--finalize", action="store_true")
     ap.add_argument("--timeout", type=int, default=900, help="seconds per child")
     ap.add_argument("--log", default="")
+    ap.add_argument("--variant", default=VARIANT, help="the baseline variant library (another paired A/B of the same "
+                    "kind, e.g. nokgroup: python -m tair_amd.build --variant nokgroup -D TAIR_NO_KGROUP)")
     a = ap.parse_args()
     sys.path.insert(0, ROOT)
     from tair_amd import build
-    if not os.path.exists(build.variant_lib(VARIANT)):
-        sys.exit(f"ffpout_bench: {build.variant_lib(VARIANT)} not built "
-                 f"(python -m tair_amd.build --variant {VARIANT} -D TAIR_NO_FFPOUT)")
+    variant = a.variant
+    if not os.path.exists(build.variant_lib(variant)):
+        sys.exit(f"ffpout_bench: {build.variant_lib(variant)} not built "
+                 f"(python -m tair_amd.build --variant {variant} -D <the macro that makes it the baseline>, e.g. "
+                 "noffpout: TAIR_NO_FFPOUT, nokgroup: TAIR_NO_KGROUP)")
     build.ensure_built()
-    hashes = dict(product=build.library_hash(), **{VARIANT: build.library_hash(build.variant_lib(VARIANT))})
+    hashes = dict(product=build.library_hash(), **{variant: build.library_hash(build.variant_lib(variant))})
     log = open(a.log, "a") if a.log else None
 
     def emit(rec):
@@ -116,17 +121,17 @@ def main():
             log.flush()
 
     if a.finalize:
-        for v in (VARIANT, ""):
+        for v in (variant, ""):
             emit(dict(run_finalize(v, a), srchash=hashes[v or "product"]))
         return
-    runs = {VARIANT: [], "product": []}
+    runs = {variant: [], "product": []}
     for i in range(a.pairs):
-        for v in (VARIANT, ""):
+        for v in ((variant, "") if i % 2 == 0 else ("", variant)):  # the order alternates from pair to pair
             rec = dict(run_bench(v, a), pair=i, srchash=hashes[v or "product"])
             runs[v or "product"].append(rec["value"])
             emit(rec)
-    gains = [p / q - 1.0 for p, q in zip(runs["product"], runs[VARIANT])]
-    base = runs[VARIANT]
+    gains = [p / q - 1.0 for p, q in zip(runs["product"], runs[variant])]
+    base = runs[variant]
     spread = (max(base) - min(base)) / statistics.median(base)
     emit(dict(kind="summary", config=a.config, pairs=a.pairs, unit="Mpix/s",
               product_median=round(statistics.median(runs["product"]), 4), variant_median=round(statistics.median(base), 4),

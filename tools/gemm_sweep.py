@@ -40,6 +40,10 @@ SHAPES = {
     # the two launches it replaces are lin*ff2 + lin*proj
     "lin64ffpo": (0, 64, 320, 1280, 320), "lin32ffpo": (0, 32, 640, 2560, 640), "lin16ffpo": (0, 16, 1280, 5120, 1280),
     "lin8ffpo": (0, 8, 1280, 5120, 1280), "lin8ff2": (0, 8, 1280, 5120, 0),
+    # decoder ResBlock conv1 over the concatenated skip (C = 2C / 3C of the level) and conv2 with the 1x1 skip conv
+    "conv64c640": (1, 64, 320, 640, 0), "conv64c960": (1, 64, 320, 960, 0), "conv32c1280": (1, 32, 640, 1280, 0),
+    "conv32c1920": (1, 32, 640, 1920, 0), "conv16c2560": (1, 16, 1280, 2560, 0), "conv32cat": (1, 32, 640, 640, 1280),
+    "conv16cat": (1, 16, 1280, 1280, 2560),
 }
 HALO_TILES = [(256, 64), (256, 128), (256, 160)]  # conv_halo_kernel (force_stages 9): stride-1 3x3, no Kx
 HALO_SPLITS = [1, 2, 3, 4, 5, 6, 8, 10, 12, 16, 20]
