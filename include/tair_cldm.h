@@ -131,6 +131,35 @@ typedef struct {
  * returns the decoder features of the cond half (rows [0,B)), and tair_sampler_get_v the guided v. */
 int tair_sampler_prepare_guided(tair_cldm* h, const tair_sampler_io* io, const tair_guidance_io* g,
                                 tair_stream_t stream);
+/* Latent tiling inside the sampling loop (utils/common.py:125-234 make_tiled_fn, wired as in
+ * ddim_sampler.py:165-180 and passed to every sampler by pipeline.py:211-213): a whole latent larger than the
+ * handle's latent_h x latent_w tile.  Every step runs the network on the overlapping tile-sized windows of
+ * the latent (sliding_windows: starts 0, stride, ... plus one flush with the edge; row-major), blends the
+ * window outputs with Gaussian weights (gaussian_weights, var 0.01) and runs p_sample on the whole latent. */
+typedef struct {
+  int height, width; /* the whole latent, H x W >= latent_h x latent_w */
+  int stride;        /* window stride in latent pixels, >= 1 */
+} tair_tiling_io;
+/* tair_sampler_prepare_guided with latent tiling.  t == NULL is exactly tair_sampler_prepare_guided.
+ * Otherwise io->batch is the number of images B (any B >= 1), io->x_T and io->c_img (and g->c_img) are
+ * [B,4,H,W], io->noise is [n_steps,B,4,H,W], and the contexts are shared by every window: c_txt_batch must
+ * be 1 for both halves.  The N = B * T window rows of a step (image-major, then window order) run as
+ * ceil(N / cap) forwards of equal row count, cap = max_batch (g == NULL) or max_batch / 2 (guided: cond
+ * rows, then uncond rows, each half blended before the guidance sum); the unused rows of the last forward
+ * repeat the last window and are never blended.  TAIR_ERR_ARG with a message: latent_h != latent_w, H or W
+ * below the tile, stride < 1, a c_txt_batch other than 1, cap == 0.  The whole-latent buffers (state, noise,
+ * hints, accumulators, blended v, weight table) are allocated here, never in tair_sampler_run; they only
+ * grow, so their addresses stay fixed across replays, and a reallocation drops the captured graphs.  After
+ * a tiled prepare: tair_sampler_run(n) runs n steps of n_chunks forwards each (one captured graph per
+ * forward, replayed with the chunk index on the device; a tiled and an untiled run never replay each
+ * other's graph), tair_sampler_get_x returns [B,4,H,W] and refuses feats (per-window decoder features have
+ * no whole-image meaning: TAIR_ERR_ARG), tair_sampler_get_v returns the blended (guided) v [B,4,H,W], and
+ * tair_sampler_set_context accepts a batch-1 context. */
+int tair_sampler_prepare_tiled(tair_cldm* h, const tair_sampler_io* io, const tair_guidance_io* g,
+                               const tair_tiling_io* t, tair_stream_t stream);
+/* The plan of the last tiled prepare: windows per image, forwards per step, window rows per forward, unused
+ * rows of the last forward (all 0 after an untiled prepare). */
+int tair_sampler_tiling_info(const tair_cldm* h, int* windows, int* chunks, int* rows_per_chunk, int* pad);
 /* Re-encodes the cross-attention K/V caches from a new c_txt (stage-3 val_sample, :317). */
 int tair_sampler_set_context(tair_cldm* h, const float* c_txt, int c_txt_batch, tair_stream_t stream);
 /* Runs n steps of p_sample (ControlNet + UNet + fused update) from the device step counter.

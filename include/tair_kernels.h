@@ -169,6 +169,42 @@ int tair_k_sampler_step(float* x, float* v, const float* v_uncond, const float* 
                         const int* counter, const float* noise, int rows, int C, void* in_u, void* in_c, int ld,
                         int ldc, int half_rows, void* stream);
 
+/* Latent tiling inside the sampling loop on caller-owned device buffers (utils/common.py:125-234
+ * make_tiled_fn; the two kernels tair_sampler_run launches around every forward of a tiled run), for a
+ * caller that drives its own loop.  Geometry: B images of a whole latent H x W, tile x tile windows at
+ * `stride` (starts 0, stride, ... plus one flush with the edge when the stride does not divide; row-major;
+ * T per image), job rows j = b * T + k run as n_chunks forwards of rows_per_chunk rows each
+ * (n_chunks * rows_per_chunk >= B * T and every chunk holds a job row; the surplus rows of the last chunk
+ * are pad).  *chunk is the current chunk, read on the device; a value outside [0, n_chunks) writes nothing.
+ * Both calls are capturable and never synchronise; a bad shape argument is -1 with a message, before any
+ * launch.
+ *
+ * tair_k_tile_gather: x [B*H*W, C] fp32 NHWC (the whole-latent state), hint [B*H*W, hint_channels] (needed
+ * with in_c).  Row r of the chunk gets its window as (hi, lo, hi) bf16 planes, hi = bf16(x), lo =
+ * bf16(x - hi): in_u[(r * tile^2 + p) * ld + {0, C, 2C} + c] and, unless in_c is NULL,
+ * in_c[... + {0, ldc, 2 ldc} + c] with the hint planes at channel C (the layout tair_k_sampler_step
+ * writes).  half_rows > 0 writes the planes again half_rows plane rows further on (the uncond half of a
+ * guided forward), with hint_uncond (NULL = hint) as that half's hint.  A pad row gets the job's last
+ * window.  Other channels of a row are left alone. */
+int tair_k_tile_gather(const float* x, const float* hint, const float* hint_uncond, const int* chunk, int B, int H,
+                       int W, int tile, int stride, int rows_per_chunk, int n_chunks, int C, int hint_channels,
+                       void* in_u, void* in_c, int ld, int ldc, int half_rows, void* stream);
+/* tair_k_tile_blend_step: v [rows_per_chunk * tile^2, C] fp32 is the forward's output for the chunk (guided,
+ * acc_uncond != NULL: the uncond half follows rows_per_chunk * tile^2 rows further on).  One thread per
+ * whole-latent element adds, over the chunk's windows that cover its pixel in ascending window order,
+ *   acc += v_k * w,  cnt += w        (weights [tile^2] fp32; acc, acc_uncond, cnt [B*H*W, C] fp32, zero at start)
+ * so the sums do not depend on the chunking; pad rows are never read.  A pixel that only one window of the
+ * job covers accumulates v itself and keeps it unchanged (the reference's fl(fl(v w) / w) is within one ulp of
+ * it; a latent of one window thereby reproduces the untiled step exactly).  On the last chunk of the step:
+ *   v = acc / cnt  (guided: v_u + scales[i] * (v_c - v_u), both halves blended first, spaced_sampler.py:149-164)
+ * is stored to v_blend [B*H*W, C], x [B*H*W, C] gets the update of tair_k_sampler_step against noise
+ * [n][B*H*W, C] with i = counter[0], n = counter[1] (i outside [0, n) writes nothing), and the accumulators
+ * are cleared.  Then *chunk advances, or returns to 0 with counter[0] += 1 after the last chunk. */
+int tair_k_tile_blend_step(float* x, const float* v, float* v_blend, float* acc, float* acc_uncond, float* cnt,
+                           const float* weights, const float* tables, const float* scales, int* counter, int* chunk,
+                           const float* noise, int B, int H, int W, int tile, int stride, int rows_per_chunk,
+                           int n_chunks, int C, void* stream);
+
 /* Overlap-blend stitch of decoded tiles on the device (val_patches.py:114-206 merge_patches_with_overlap,
  * stride generalised): tiles [n_tiles][C][patch][patch] fp32 on a raster nh x nw grid, out [C][H][W]
  * fp32 cropped; rtab[i] = fp32((i+1)/overlap), i < overlap (device).  Bitwise the reference loop. */

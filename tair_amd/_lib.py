@@ -81,6 +81,11 @@ class GuidanceIO(ctypes.Structure):
     ]
 
 
+class TilingIO(ctypes.Structure):
+    """tair_tiling_io: the whole latent of a tiled sampler run and the window stride."""
+    _fields_ = [("height", ctypes.c_int), ("width", ctypes.c_int), ("stride", ctypes.c_int)]
+
+
 class GemmDesc(ctypes.Structure):
     _fields_ = [(n, ctypes.c_int) for n in ("M", "N", "K", "amode")] + [
         ("A", ctypes.c_void_p), ("lda", ctypes.c_int), ("C", ctypes.c_int), ("Bn", ctypes.c_int),
@@ -126,6 +131,10 @@ SIGNATURES = {
     "tair_sampler_set_schedule": (_I, [_P, _I, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_float)]),
     "tair_sampler_prepare": (_I, [_P, ctypes.POINTER(SamplerIO), _P]),
     "tair_sampler_prepare_guided": (_I, [_P, ctypes.POINTER(SamplerIO), ctypes.POINTER(GuidanceIO), _P]),
+    "tair_sampler_prepare_tiled": (_I, [_P, ctypes.POINTER(SamplerIO), ctypes.POINTER(GuidanceIO),
+                                        ctypes.POINTER(TilingIO), _P]),
+    "tair_sampler_tiling_info": (_I, [_P, ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I),
+                                      ctypes.POINTER(_I)]),
     "tair_sampler_set_context": (_I, [_P, _P, _I, _P]),
     "tair_sampler_run": (_I, [_P, _I, _I, _P]),
     "tair_sampler_get_x": (_I, [_P, _P, _P, _P]),
@@ -160,6 +169,9 @@ SIGNATURES = {
     "tair_k_quant_rows_fp8_ex": (_I, [_P, _I, _I, _I, _I, _P, _P, _I, _I, _P, _P]),
     "tair_k_gn_apply_fp8": (_I, [_P, _I, _I, _I, _I, _I, _I, ctypes.c_float, _P, _P, _I, _P, _I, _P, _P, _I, _P]),
     "tair_k_sampler_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _I, _P, _P, _I, _I, _I, _P]),
+    "tair_k_tile_gather": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _P]),
+    "tair_k_tile_blend_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I,
+                                    _P]),
     "tair_k_merge_overlap": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P]),
     "tair_k_stitch_peers": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P]),
     "tair_ipc_get_handle": (_I, [_P, _P, ctypes.POINTER(ctypes.c_ulonglong)]),

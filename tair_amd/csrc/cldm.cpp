@@ -356,6 +356,22 @@ struct tair_cldm {
   int graph_control = -1, graph_ctx_bstride = -1;  // context batch stride and the zero-conv scales
   int graph_guided = -1;                  // guided or not (the guidance scales are read from cfg_scales)
   float graph_scales[13] = {};
+  // latent tiling (tair_sampler_prepare_tiled): the whole-latent buffers only grow, so the addresses the
+  // captured chunk graph holds stay fixed; a reallocation drops the graphs
+  int tl_on = 0;                          // the last prepare was tiled
+  TileGeom tl_g{};                        // images, whole latent, tile, stride, rows per chunk, chunks
+  int tl_T = 0, tl_pad = 0;               // windows per image, unused rows of the last chunk
+  int tl_hint_u_on = 0;                   // the uncond half has a hint of its own
+  size_t tl_cap_px = 0, tl_cap_noise = 0; // capacity: pixels B*H*W of the per-pixel buffers, floats of the noise
+  float *tl_x = nullptr, *tl_noise = nullptr, *tl_hint = nullptr, *tl_hint_u = nullptr;
+  float *tl_acc = nullptr, *tl_acc_u = nullptr, *tl_cnt = nullptr, *tl_v = nullptr;
+  float* tl_w = nullptr;                  // [S*S] fp32 Gaussian blend weights
+  int* tl_chunk = nullptr;                // device chunk index of the current step
+  hipGraph_t tl_graph = nullptr;          // one chunk: gather -> body -> blend / step
+  hipGraphExec_t tl_gexec = nullptr;
+  TileGeom graph_tl_g{};                  // what the captured chunk froze
+  int graph_tl_control = -1, graph_tl_guided = -1, graph_tl_hint_u = -1;
+  float graph_tl_scales[13] = {};
   // instrumentation
   bool dry = false;
   // TAIR_ABLATE (timing experiments only, never set in tests or the bench line): bit c skips every
@@ -2118,6 +2134,9 @@ int tair_cldm_destroy(tair_cldm* h) {
   if (h->sched_tabs) hipFree(h->sched_tabs);
   if (h->noise) hipFree(h->noise);
   if (h->sched_t_dev) hipFree(h->sched_t_dev);
+  for (void* p : {(void*)h->tl_x, (void*)h->tl_noise, (void*)h->tl_hint, (void*)h->tl_hint_u, (void*)h->tl_acc,
+                  (void*)h->tl_acc_u, (void*)h->tl_cnt, (void*)h->tl_v, (void*)h->tl_w, (void*)h->tl_chunk})
+    if (p) hipFree(p);
   delete h;
   return TAIR_OK;
 }
@@ -2622,6 +2641,7 @@ int tair_sampler_prepare_guided(tair_cldm* h, const tair_sampler_io* io, const t
   const int HW = h->lev_h[0] * h->lev_w[0];
   const int C = h->cfg.in_channels, hc = h->cfg.hint_channels;
   h->s_batch = B;
+  h->tl_on = 0;
   h->s_guided = g != nullptr;
   h->s_ctx_bstride = (g || io->c_txt_batch != 1) ? h->cfg.context_len : 0;
   h->s_control = io->c_img != nullptr;
@@ -2675,14 +2695,14 @@ int tair_sampler_set_context(tair_cldm* h, const float* c_txt, int c_txt_batch, 
   tair::g_err[0] = 0;
   int rc = check_ready(h);
   if (rc) return rc;
-  if (!c_txt || (c_txt_batch != 1 && c_txt_batch != h->s_batch)) {
-    set_error("set_context: bad arguments");
+  if (!c_txt || (c_txt_batch != 1 && (h->tl_on || c_txt_batch != h->s_batch))) {
+    set_error(h->tl_on ? "set_context: a tiled run shares one context (c_txt_batch 1)" : "set_context: bad arguments");
     return TAIR_ERR_ARG;
   }
   hipStream_t s = (hipStream_t)stream;
   hipError_t e;
   if (h->s_guided) {  // the cond half only (tiles [0, B), always laid out per tile); the negative context stays
-    const int B = h->s_batch;
+    const int B = h->tl_on ? h->tl_g.rows_per_chunk : h->s_batch;  // rows of one half of the forward
     auto run = [&]() -> hipError_t {
       TRY(put_ctx_tiles(h, c_txt, c_txt_batch, B, 0, s));
       TRY(kv_caches(h, h->unet, B * h->cfg.context_len, s));
@@ -2735,6 +2755,295 @@ static void drop_step_graphs(tair_cldm* h) {
   if (h->graph) hipGraphDestroy(h->graph);
   h->gexec = nullptr;
   h->graph = nullptr;
+  if (h->tl_gexec) hipGraphExecDestroy(h->tl_gexec);
+  if (h->tl_graph) hipGraphDestroy(h->tl_graph);
+  h->tl_gexec = nullptr;
+  h->tl_graph = nullptr;
+}
+
+// ---- latent tiling (include/tair_cldm.h tair_sampler_prepare_tiled) ---------------------------------------
+// gaussian_weights(S, S) of utils/common.py:144-171 in float64, cast to fp32: var 0.01, column midpoint
+// (S - 1) / 2, row midpoint S / 2 (the reference's asymmetry)
+static std::vector<float> tile_weights(int S) {
+  const double var = 0.01, norm = std::sqrt(2.0 * 3.141592653589793238462643383279502884 * var);
+  std::vector<double> xp(S), yp(S);
+  for (int i = 0; i < S; ++i) {
+    const double dx = i - (S - 1) / 2.0, dy = i - S / 2.0;
+    xp[i] = std::exp(-dx * dx / ((double)S * S) / (2 * var)) / norm;
+    yp[i] = std::exp(-dy * dy / ((double)S * S) / (2 * var)) / norm;
+  }
+  std::vector<float> w((size_t)S * S);
+  for (int y = 0; y < S; ++y)
+    for (int x = 0; x < S; ++x) w[(size_t)y * S + x] = (float)(yp[y] * xp[x]);
+  return w;
+}
+
+// Grow-only whole-latent buffers: px pixels (B*H*W) and noise_floats floats of noise.  Returns false when an
+// allocation fails; a reallocation drops the captured graphs (they hold the old addresses).
+static bool tile_reserve(tair_cldm* h, size_t px, size_t noise_floats) {
+  const size_t C = h->cfg.in_channels, hc = h->cfg.hint_channels, S = h->cfg.latent_h;
+  if (!h->tl_chunk && hipMalloc(&h->tl_chunk, 16) != hipSuccess) return false;
+  if (!h->tl_w && hipMalloc(&h->tl_w, S * S * 4) != hipSuccess) return false;
+  if (px > h->tl_cap_px) {
+    drop_step_graphs(h);
+    float** per_c[] = {&h->tl_x, &h->tl_acc, &h->tl_acc_u, &h->tl_cnt, &h->tl_v};
+    float** per_h[] = {&h->tl_hint, &h->tl_hint_u};
+    h->tl_cap_px = 0;
+    for (float** p : per_c) {
+      if (*p) hipFree(*p);
+      *p = nullptr;
+    }
+    for (float** p : per_h) {
+      if (*p) hipFree(*p);
+      *p = nullptr;
+    }
+    for (float** p : per_c)
+      if (hipMalloc(p, px * C * 4) != hipSuccess) return false;
+    for (float** p : per_h)
+      if (hipMalloc(p, px * hc * 4) != hipSuccess) return false;
+    h->tl_cap_px = px;
+  }
+  if (noise_floats > h->tl_cap_noise) {
+    drop_step_graphs(h);
+    if (h->tl_noise) hipFree(h->tl_noise);
+    h->tl_noise = nullptr;
+    h->tl_cap_noise = 0;
+    if (hipMalloc(&h->tl_noise, noise_floats * 4) != hipSuccess) return false;
+    h->tl_cap_noise = noise_floats;
+  }
+  return true;
+}
+
+int tair_sampler_prepare_tiled(tair_cldm* h, const tair_sampler_io* io, const tair_guidance_io* g,
+                               const tair_tiling_io* t, tair_stream_t stream) {
+  if (!t) return tair_sampler_prepare_guided(h, io, g, stream);
+  tair::g_err[0] = 0;
+  int rc = check_ready(h);
+  if (rc) return rc;
+  if (!h->n_steps) {
+    set_error("sampler_prepare_tiled: call tair_sampler_set_schedule first");
+    return TAIR_ERR_STATE;
+  }
+  if (!io || !io->x_T || !io->noise || !io->c_txt || io->batch < 1) {
+    set_error("sampler_prepare_tiled: bad io");
+    return TAIR_ERR_ARG;
+  }
+  const int S = h->cfg.latent_h;
+  if (h->cfg.latent_h != h->cfg.latent_w) {
+    set_error("sampler_prepare_tiled: the handle's tile is %dx%d; latent tiling needs a square tile", h->cfg.latent_h,
+              h->cfg.latent_w);
+    return TAIR_ERR_ARG;
+  }
+  if (t->height < S || t->width < S) {
+    set_error("sampler_prepare_tiled: the latent %dx%d is smaller than the tile %dx%d", t->height, t->width, S, S);
+    return TAIR_ERR_ARG;
+  }
+  if (t->stride < 1) {
+    set_error("sampler_prepare_tiled: stride %d must be >= 1", t->stride);
+    return TAIR_ERR_ARG;
+  }
+  if (io->c_txt_batch != 1 || (g && g->c_txt_batch != 1)) {
+    set_error("sampler_prepare_tiled: the windows share one context: c_txt_batch must be 1 (cond %d, uncond %d)",
+              io->c_txt_batch, g ? g->c_txt_batch : 1);
+    return TAIR_ERR_ARG;
+  }
+  if (g && (!g->c_txt || !g->scales)) {
+    set_error("sampler_prepare_tiled: bad guidance (c_txt %p, scales %p)", (const void*)g->c_txt,
+              (const void*)g->scales);
+    return TAIR_ERR_ARG;
+  }
+  if (g && g->c_img && !io->c_img) {
+    set_error("sampler_prepare_tiled: the uncond half has a c_img and the cond half none (ControlNet runs for both "
+              "halves or for neither)");
+    return TAIR_ERR_ARG;
+  }
+  const int cap = g ? h->cfg.max_batch / 2 : h->cfg.max_batch;
+  if (cap < 1) {
+    set_error("sampler_prepare_tiled: max_batch %d leaves no room for a guided window row (2 rows per window)",
+              h->cfg.max_batch);
+    return TAIR_ERR_ARG;
+  }
+  const int B = io->batch, H = t->height, W = t->width;
+  const int C = h->cfg.in_channels, hc = h->cfg.hint_channels;
+  const long T = tile_windows(H, W, S, t->stride);
+  const long N = (long)B * T;
+  const size_t px = (size_t)B * H * W;
+  if (N > 0x7fffffffL || px * (size_t)std::max(C, hc) > 0x7fffffffUL) {
+    set_error("sampler_prepare_tiled: %d images of %dx%d are too large", B, H, W);
+    return TAIR_ERR_ARG;
+  }
+  const int n_chunks = (int)((N + cap - 1) / cap);
+  const int rpc = (int)((N + n_chunks - 1) / n_chunks);
+  if (!tile_reserve(h, px, (size_t)h->n_steps * px * C)) {
+    set_error("sampler_prepare_tiled: cannot allocate the whole-latent buffers (%d x %dx%d)", B, H, W);
+    return TAIR_ERR_HIP;
+  }
+  hipStream_t s = (hipStream_t)stream;
+  h->s_batch = B;
+  h->tl_on = 1;
+  h->tl_g = TileGeom{B, H, W, S, t->stride, rpc, n_chunks};
+  h->tl_T = (int)T;
+  h->tl_pad = (int)((long)n_chunks * rpc - N);
+  h->tl_hint_u_on = g && g->c_img;
+  h->s_guided = g != nullptr;
+  h->s_ctx_bstride = g ? h->cfg.context_len : 0;
+  h->s_control = io->c_img != nullptr;
+  for (int i = 0; i < 13; ++i) h->s_scales[i] = io->control_scales ? io->control_scales[i] : 1.f;
+  const std::vector<float> w = tile_weights(S);
+  auto to_nhwc = [&](const float* src, int ch, float* dst) {
+    const long n = (long)px * ch;
+    hipLaunchKernelGGL(nchw2nhwc_f32_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, s, src, B, ch, H * W, dst);
+    return hipGetLastError();
+  };
+  auto run = [&]() -> hipError_t {
+    TRY(time_tables(h, h->unet, h->sched_t_dev, h->n_steps, h->tab_u, s));
+    if (h->s_control) TRY(time_tables(h, h->cn, h->sched_t_dev, h->n_steps, h->tab_c, s));
+    if (g) {  // rows [0, rpc) cond, [rpc, 2 rpc) uncond of every chunk: the K/V caches are written once, here
+      TRY(put_ctx_tiles(h, io->c_txt, 1, rpc, 0, s));
+      TRY(put_ctx_tiles(h, g->c_txt, 1, rpc, rpc, s));
+      TRY(kv_caches(h, h->unet, 2 * rpc * h->cfg.context_len, s));
+      TRY(kv_caches(h, h->cn, 2 * rpc * h->cfg.context_len, s));
+      TRY(hipMemcpyAsync(h->cfg_scales, g->scales, (size_t)h->n_steps * 4, hipMemcpyHostToDevice, s));
+    } else {
+      TRY(prepare_ctx(h, io->c_txt, 1, s));
+    }
+    TRY(hipMemcpyAsync(h->tl_w, w.data(), w.size() * 4, hipMemcpyHostToDevice, s));
+    TRY(hipStreamSynchronize(s));  // the host copies above are done before their sources go away
+    TRY(to_nhwc(io->x_T, C, h->tl_x));
+    if (h->s_control) TRY(to_nhwc(io->c_img, hc, h->tl_hint));
+    if (h->tl_hint_u_on) TRY(to_nhwc(g->c_img, hc, h->tl_hint_u));
+    for (int i = 0; i < h->n_steps; ++i)
+      TRY(to_nhwc(io->noise + (size_t)i * px * C, C, h->tl_noise + (size_t)i * px * C));
+    TRY(hipMemsetAsync(h->tl_acc, 0, px * C * 4, s));
+    TRY(hipMemsetAsync(h->tl_acc_u, 0, px * C * 4, s));
+    TRY(hipMemsetAsync(h->tl_cnt, 0, px * C * 4, s));
+    TRY(hipMemsetAsync(h->tl_v, 0, px * C * 4, s));
+    TRY(hipMemsetAsync(h->tl_chunk, 0, 16, s));
+    hipLaunchKernelGGL(init_counter_kernel, dim3(1), dim3(64), 0, s, h->counter, h->n_steps);
+    return hipGetLastError();
+  };
+  hipError_t e = run();
+  if (e != hipSuccess) return fail_hip(e);
+  return TAIR_OK;
+}
+
+int tair_sampler_tiling_info(const tair_cldm* h, int* windows, int* chunks, int* rows_per_chunk, int* pad) {
+  tair::g_err[0] = 0;
+  if (!h || !windows || !chunks || !rows_per_chunk || !pad) {
+    set_error("tiling_info: null argument");
+    return TAIR_ERR_ARG;
+  }
+  *windows = h->tl_on ? h->tl_T : 0;
+  *chunks = h->tl_on ? h->tl_g.n_chunks : 0;
+  *rows_per_chunk = h->tl_on ? h->tl_g.rows_per_chunk : 0;
+  *pad = h->tl_on ? h->tl_pad : 0;
+  return TAIR_OK;
+}
+
+// One forward of a tiled step: the windows of the current chunk are gathered from the whole latent, the
+// network runs on them, and the blend kernel accumulates the outputs (on the step's last chunk it also runs
+// the sampler update on the whole latent and advances the step counter).
+static hipError_t sampler_one_chunk(tair_cldm* h, hipStream_t s) {
+  const TileGeom& tg = h->tl_g;
+  const int rpc = tg.rows_per_chunk;
+  const int nb = h->s_guided ? 2 * rpc : rpc;  // rows the net runs: cond [0, rpc), uncond [rpc, 2 rpc)
+  const int C = h->cfg.in_channels, hc = h->cfg.hint_channels;
+  TileGatherArgs ga{};
+  ga.x = h->tl_x;
+  ga.hint = h->s_control ? h->tl_hint : nullptr;
+  ga.hint_u = h->tl_hint_u_on ? h->tl_hint_u : nullptr;
+  ga.chunk = h->tl_chunk;
+  ga.in_u = h->in_u;
+  ga.in_c = h->s_control ? h->in_c : nullptr;
+  ga.C = C;
+  ga.hc = hc;
+  ga.ld = CONVIN_LD;
+  ga.ldc = C + hc;
+  ga.half_rows = h->s_guided ? rpc * tg.S * tg.S : 0;
+  ga.g = tg;
+  TRY(launch(h, 4, 0, s, [&] { return tile_gather(ga, s); }));
+  hipLaunchKernelGGL(set_rows_kernel, dim3(1), dim3(std::max(64, ((nb + 63) / 64) * 64)), 0, s, h->counter,
+                     h->rows_step, nb);
+  TRY(hipGetLastError());
+  const Fwd f = make_fwd(h, s, nb, h->rows_step, h->s_ctx_bstride, h->s_control);
+  TRY(body(h, f, h->s_control, h->s_scales));
+  TileBlendArgs ba{};
+  ba.x = h->tl_x;
+  ba.v = h->v_out;
+  ba.v_blend = h->tl_v;
+  ba.acc = h->tl_acc;
+  ba.acc_u = h->s_guided ? h->tl_acc_u : nullptr;
+  ba.cnt = h->tl_cnt;
+  ba.w = h->tl_w;
+  ba.tabs = h->sched_tabs;
+  ba.scales = h->cfg_scales;
+  ba.counter = h->counter;
+  ba.chunk = h->tl_chunk;
+  ba.noise = h->tl_noise;
+  ba.C = C;
+  ba.g = tg;
+  return launch(h, 4, 0, s, [&] { return tile_blend_step(ba, s); });
+}
+
+static bool same_geom(const TileGeom& a, const TileGeom& b) {
+  return a.B == b.B && a.H == b.H && a.W == b.W && a.S == b.S && a.stride == b.stride &&
+         a.rows_per_chunk == b.rows_per_chunk && a.n_chunks == b.n_chunks;
+}
+
+// n_steps tiled steps of n_chunks forwards each.  One chunk is captured once and replayed with the chunk index
+// and the step counter on the device, so the graph stays the size of one forward whatever the image size.
+static int sampler_run_tiled(tair_cldm* h, int n_steps, int use_graph, hipStream_t cs) {
+  hipError_t e = hipSuccess;
+  const long launches = (long)n_steps * h->tl_g.n_chunks;
+  if (use_graph && !h->prof && !h->dry) {
+    hipStream_t s = h->gstream;
+    e = hipEventRecord(h->ev_in, cs);
+    if (e == hipSuccess) e = hipStreamWaitEvent(s, h->ev_in, 0);
+    if (e != hipSuccess) return fail_hip(e);
+    // the captured chunk bakes in the geometry (images, whole latent, stride, rows per chunk, chunks), whether
+    // the ControlNet branch runs, guided or not, whose hint the uncond half reads, and the control scales
+    const bool same = h->tl_gexec != nullptr && same_geom(h->graph_tl_g, h->tl_g) &&
+                      h->graph_tl_control == h->s_control && h->graph_tl_guided == h->s_guided &&
+                      h->graph_tl_hint_u == h->tl_hint_u_on &&
+                      std::memcmp(h->graph_tl_scales, h->s_scales, sizeof(h->s_scales)) == 0;
+    if (!same) {
+      if (h->tl_gexec) hipGraphExecDestroy(h->tl_gexec);
+      if (h->tl_graph) hipGraphDestroy(h->tl_graph);
+      h->tl_gexec = nullptr;
+      h->tl_graph = nullptr;
+      e = hipStreamBeginCapture(s, hipStreamCaptureModeRelaxed);
+      if (e != hipSuccess) return fail_hip(e);
+      hipError_t ce = sampler_one_chunk(h, s);
+      hipGraph_t g = nullptr;
+      e = hipStreamEndCapture(s, &g);
+      if (ce != hipSuccess) {
+        if (g) hipGraphDestroy(g);
+        return fail_hip(ce);
+      }
+      if (e != hipSuccess) return fail_hip(e);
+      h->tl_graph = g;
+      e = hipGraphInstantiate(&h->tl_gexec, g, nullptr, nullptr, 0);
+      if (e != hipSuccess) return fail_hip(e);
+      h->graph_tl_g = h->tl_g;
+      h->graph_tl_control = h->s_control;
+      h->graph_tl_guided = h->s_guided;
+      h->graph_tl_hint_u = h->tl_hint_u_on;
+      std::memcpy(h->graph_tl_scales, h->s_scales, sizeof(h->s_scales));
+    }
+    for (long i = 0; i < launches; ++i) {
+      e = hipGraphLaunch(h->tl_gexec, s);
+      if (e != hipSuccess) return fail_hip(e);
+    }
+    e = hipEventRecord(h->ev_out, s);
+    if (e == hipSuccess) e = hipStreamWaitEvent(cs, h->ev_out, 0);
+    if (e != hipSuccess) return fail_hip(e);
+    return TAIR_OK;
+  }
+  for (long i = 0; i < launches; ++i) {
+    e = sampler_one_chunk(h, cs);
+    if (e != hipSuccess) return fail_hip(e);
+  }
+  return TAIR_OK;
 }
 
 int tair_sampler_run(tair_cldm* h, int n_steps, int use_graph, tair_stream_t stream) {
@@ -2745,6 +3054,7 @@ int tair_sampler_run(tair_cldm* h, int n_steps, int use_graph, tair_stream_t str
     set_error("sampler_run: call tair_sampler_prepare first");
     return TAIR_ERR_STATE;
   }
+  if (h->tl_on) return sampler_run_tiled(h, n_steps, use_graph, (hipStream_t)stream);
   hipStream_t cs = (hipStream_t)stream;
   hipError_t e = hipSuccess;
   if (use_graph && !h->prof && !h->dry) {
@@ -2803,6 +3113,14 @@ int tair_sampler_get_x(tair_cldm* h, float* x_out, float* feats[4], tair_stream_
     return TAIR_ERR_ARG;
   }
   hipStream_t s = (hipStream_t)stream;
+  if (h->tl_on) {  // the whole latent [B,4,H,W]
+    if (feats) {
+      set_error("get_x: a tiled run has no decoder features (they are per window, not per image)");
+      return TAIR_ERR_ARG;
+    }
+    hipError_t et = nhwc_f32_to_nchw_f32(h->tl_x, h->s_batch, h->cfg.in_channels, h->tl_g.H * h->tl_g.W, x_out, s);
+    return et != hipSuccess ? fail_hip(et) : TAIR_OK;
+  }
   const int HW = h->lev_h[0] * h->lev_w[0];
   hipError_t e = nhwc_f32_to_nchw_f32(h->xs, h->s_batch, h->cfg.in_channels, HW, x_out, s);
   if (e != hipSuccess) return fail_hip(e);
@@ -2819,8 +3137,9 @@ int tair_sampler_get_v(tair_cldm* h, float* v_out, tair_stream_t stream) {
     set_error("get_v: bad state");
     return TAIR_ERR_ARG;
   }
-  const int HW = h->lev_h[0] * h->lev_w[0];
-  hipError_t e = nhwc_f32_to_nchw_f32(h->v_out, h->s_batch, h->cfg.out_channels, HW, v_out, (hipStream_t)stream);
+  const int HW = h->tl_on ? h->tl_g.H * h->tl_g.W : h->lev_h[0] * h->lev_w[0];  // tiled: the blended v
+  hipError_t e = nhwc_f32_to_nchw_f32(h->tl_on ? h->tl_v : h->v_out, h->s_batch, h->cfg.out_channels, HW, v_out,
+                                      (hipStream_t)stream);
   if (e != hipSuccess) return fail_hip(e);
   return TAIR_OK;
 }

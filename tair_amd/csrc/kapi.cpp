@@ -172,6 +172,36 @@ int tair_k_sampler_step(float* x, float* v, const float* v_uncond, const float* 
   return e == hipSuccess ? 0 : -2;
 }
 
+int tair_k_tile_gather(const float* x, const float* hint, const float* hint_uncond, const int* chunk, int B, int H,
+                       int W, int tile, int stride, int rows_per_chunk, int n_chunks, int C, int hint_channels,
+                       void* in_u, void* in_c, int ld, int ldc, int half_rows, void* stream) {
+  TileGatherArgs a{x, hint, hint_uncond, chunk, (bf16*)in_u, (bf16*)in_c, C, hint_channels, ld, ldc, half_rows,
+                   TileGeom{B, H, W, tile, stride, rows_per_chunk, n_chunks}};
+  const hipError_t e = tile_gather(a, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) {
+    set_error("tile_gather: bad arguments (B %d, latent %dx%d, tile %d, stride %d, rows_per_chunk %d, n_chunks %d, "
+              "C %d, hint_channels %d, ld %d, ldc %d, half_rows %d)", B, H, W, tile, stride, rows_per_chunk, n_chunks,
+              C, hint_channels, ld, ldc, half_rows);
+    return -1;
+  }
+  return e == hipSuccess ? 0 : -2;
+}
+
+int tair_k_tile_blend_step(float* x, const float* v, float* v_blend, float* acc, float* acc_uncond, float* cnt,
+                           const float* weights, const float* tables, const float* scales, int* counter, int* chunk,
+                           const float* noise, int B, int H, int W, int tile, int stride, int rows_per_chunk,
+                           int n_chunks, int C, void* stream) {
+  TileBlendArgs a{x, v, v_blend, acc, acc_uncond, cnt, weights, tables, scales, counter, chunk, noise, C,
+                  TileGeom{B, H, W, tile, stride, rows_per_chunk, n_chunks}};
+  const hipError_t e = tile_blend_step(a, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) {
+    set_error("tile_blend_step: bad arguments (B %d, latent %dx%d, tile %d, stride %d, rows_per_chunk %d, "
+              "n_chunks %d, C %d, guided %d)", B, H, W, tile, stride, rows_per_chunk, n_chunks, C, acc_uncond != nullptr);
+    return -1;
+  }
+  return e == hipSuccess ? 0 : -2;
+}
+
 int tair_k_merge_overlap(const float* tiles, int n_tiles, int nh, int nw, int patch, int overlap, int stride,
                          float* out, int C, int H, int W, const float* rtab, void* stream) {
   return merge_overlap(tiles, n_tiles, nh, nw, patch, overlap, stride, out, C, H, W, rtab, (hipStream_t)stream) ==

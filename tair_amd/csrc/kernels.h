@@ -336,6 +336,39 @@ struct SamplerUpdateArgs {
 };
 hipError_t sampler_update(const SamplerUpdateArgs& a, hipStream_t s);
 
+// ---- latent tiling inside the sampling loop (tiled.hip; utils/common.py:125-234) -----------------
+// The whole latent [B, H, W] in S x S windows at `stride` (plus one flush with the edge when the stride does
+// not divide): T windows per image, job rows j = b * T + k, run as n_chunks forwards of rows_per_chunk rows
+// (n_chunks * rows_per_chunk >= B * T, every chunk holds a job row; the surplus rows of the last are pad).
+struct TileGeom {
+  int B, H, W, S, stride, rows_per_chunk, n_chunks;
+};
+int tile_windows(int H, int W, int S, int stride);  // T, or 0 for a bad geometry
+// The (hi, lo, hi) bf16 input planes (the layout sampler_update writes) of the windows of chunk *chunk, from
+// the whole-latent NHWC fp32 state x [B*H*W, C] and hint [B*H*W, hc] (with in_c); half_rows > 0 writes the
+// planes again half_rows plane rows further on, with hint_u (NULL = hint) as that half's hint.  A pad row
+// gets the job's last window; a chunk index outside [0, n_chunks) writes nothing.
+struct TileGatherArgs {
+  const float* x; const float* hint; const float* hint_u; const int* chunk;
+  bf16* in_u; bf16* in_c;
+  int C, hc, ld, ldc, half_rows;
+  TileGeom g;
+};
+hipError_t tile_gather(const TileGatherArgs& a, hipStream_t s);
+// Accumulates chunk *chunk of the network output v [rows_per_chunk * S * S, C] (guided, acc_u != NULL: the
+// uncond half follows at rows_per_chunk * S * S rows) into acc / acc_u / cnt [B*H*W, C] with the weights
+// w [S * S]; on the step's last chunk v_blend = acc / cnt (guided: v_u + scales[i] (v_c - v_u)), x gets the
+// sampler_update arithmetic against noise [n_steps][B*H*W, C] and the accumulators are cleared.  (A pixel only
+// one window covers keeps that window's v unchanged instead of fl(fl(v w) / w).)  Then the
+// chunk index advances, or returns to 0 with counter[0] += 1 after the last chunk.
+struct TileBlendArgs {
+  float* x; const float* v; float* v_blend; float* acc; float* acc_u; float* cnt;
+  const float* w; const float* tabs; const float* scales; int* counter; int* chunk; const float* noise;
+  int C;
+  TileGeom g;
+};
+hipError_t tile_blend_step(const TileBlendArgs& a, hipStream_t s);
+
 // Multi-scale deformable attention sampling (TESTR, msda.hip): level shapes by value (capturable)
 constexpr int MSDA_MAX_LEVELS = 8;
 struct MsdaArgs {

@@ -14,6 +14,13 @@ Noise: the reference draws ``randn_like(x)`` from the global RNG inside every p_
 (spaced_sampler.py:186).  Here the per-step noise is an explicit ``noise=[steps, B, 4, h, w]``
 tensor (drawn from torch's RNG on the device when omitted), so results do not depend on batching or
 sharding.
+
+Latent tiling (``tiled=True``, utils/common.py:125-234 make_tiled_fn as wired in ddim_sampler.py:165-180): a
+latent larger than the handle's tile runs the network per step on its overlapping tile-sized windows, blends
+the window outputs with Gaussian weights and updates the whole latent, all inside the library: the B x T
+window rows of a step run as equal chunks of at most ``max_batch`` rows (half that when guided), one captured
+graph per chunk.  ``last_tiling`` holds the plan of the last ``sample``; ``_sample_tiled_host`` is the same job
+as a host loop (the baseline tools/tiled_bench.py measures against).
 """
 from __future__ import annotations
 
@@ -28,6 +35,7 @@ from . import _lib
 from .cldm import ControlLDM, _stream_ptr, feat_shapes
 from .diffusion import spaced_tables
 from .clip import tokenize
+from .tiling import gaussian_weights, plan_latent_tiles
 from .testr import GraphedSpotter, GraphedTextEncoder, TransformerDetector, decode
 
 
@@ -60,6 +68,9 @@ class SpacedSampler:
         self.timesteps = None
         self.tables: Dict[str, np.ndarray] = {}
         self.last_guided_fused: Optional[bool] = None  # the last `sample`: guided in the step graph (None: unguided)
+        # the last `sample`: the tiled plan dict(windows=per image, chunks=forwards per step, rows=window rows per
+        # forward, pad=unused rows of the last forward), None when untiled
+        self.last_tiling: Optional[Dict[str, int]] = None
 
     # sampler.py:31-38
     def get_cfg_scale(self, default_cfg_scale: float, model_t: int) -> float:
@@ -92,7 +103,7 @@ class SpacedSampler:
     # ------------------------------------------------------------------ fused path
     def _setup(self, model: ControlLDM, steps: int, x_T: torch.Tensor, cond: Dict[str, torch.Tensor],
                noise: Optional[torch.Tensor], uncond: Optional[Dict[str, torch.Tensor]] = None,
-               cfg_scales: Optional[np.ndarray] = None):
+               cfg_scales: Optional[np.ndarray] = None, tile_stride: Optional[int] = None):
         if self.parameterization not in ("v", "eps"):
             raise NotImplementedError(f"parameterization {self.parameterization!r} (spaced_sampler.py:182-185: v or eps)")
         self.make_schedule(steps)
@@ -124,7 +135,14 @@ class SpacedSampler:
         scales = _lib.float_array(model.control_scales)
         io.control_scales = ctypes.cast(scales, ctypes.POINTER(ctypes.c_float))
         self._keep = (x_T, noise, c_txt, c_img)  # alive until prepare's kernels ran
+        til = None
+        if tile_stride is not None:  # x_T, c_img and the noise are the whole latent's; the library windows them
+            til = _lib.TilingIO(int(x_T.shape[2]), int(x_T.shape[3]), int(tile_stride))
         if uncond is None:
+            if til is not None:
+                _lib.check(L.tair_sampler_prepare_tiled(model._h, ctypes.byref(io), None, ctypes.byref(til),
+                                                        _stream_ptr(dev)), "sampler_prepare_tiled")
+                return B
             _lib.check(L.tair_sampler_prepare(model._h, ctypes.byref(io), _stream_ptr(dev)), "sampler_prepare")
             return B
         # guided: the negative prompt's half; c_img NULL = the cond's (the usual case: same storage)
@@ -145,6 +163,10 @@ class SpacedSampler:
         g.c_img = None if u_img is None else u_img.data_ptr()
         g.scales = cfg_scales.ctypes.data_as(ctypes.POINTER(ctypes.c_float))
         self._keep += (u_txt, u_img)
+        if til is not None:
+            _lib.check(L.tair_sampler_prepare_tiled(model._h, ctypes.byref(io), ctypes.byref(g), ctypes.byref(til),
+                                                    _stream_ptr(dev)), "sampler_prepare_tiled")
+            return B
         _lib.check(L.tair_sampler_prepare_guided(model._h, ctypes.byref(io), ctypes.byref(g), _stream_ptr(dev)),
                    "sampler_prepare_guided")
         return B
@@ -170,15 +192,46 @@ class SpacedSampler:
                    "sampler_get_v")
         return v
 
+    def _plan_tiled(self, model: ControlLDM, x_T: torch.Tensor, cond, uncond, guided: bool, tile_size: int,
+                    tile_stride: int) -> Dict:
+        """The argument rules of a tiled run and its plan (tiling.plan_latent_tiles); ValueError names the rule."""
+        if tuple(model.latent_hw) != (tile_size, tile_size):
+            raise ValueError(f"tile_size {tile_size} must equal the model's latent size {tuple(model.latent_hw)} "
+                             "(the handle's workspace is built for one tile size)")
+        B, _, H, W = x_T.shape
+        if H < tile_size or W < tile_size:
+            raise ValueError(f"tiled sampling: the latent {H}x{W} is smaller than the tile {tile_size}")
+        for name, c in (("cond", cond), ("uncond", uncond if guided else None)):
+            if c is not None and c["c_txt"].shape[0] != 1:
+                raise ValueError(f"tiled sampling shares one prompt over all windows: {name} c_txt batch "
+                                 f"{c['c_txt'].shape[0]} must be 1")
+        plan = plan_latent_tiles(B, H, W, tile_size, tile_stride, model.max_batch, guided)
+        self.last_tiling = dict(windows=len(plan["windows"]), chunks=plan["n_chunks"], rows=plan["rows_per_chunk"],
+                                pad=plan["pad"])
+        return plan
+
+    def tiling_info(self, model: ControlLDM) -> Dict[str, int]:
+        """The library's plan of the last tiled prepare (tair_sampler_tiling_info), keyed as `last_tiling`."""
+        v = [ctypes.c_int(0) for _ in range(4)]
+        _lib.check(model._L.tair_sampler_tiling_info(model._h, *[ctypes.byref(x) for x in v]), "tiling_info")
+        return dict(windows=v[0].value, chunks=v[1].value, rows=v[2].value, pad=v[3].value)
+
     @torch.no_grad()
     def sample_trace(self, model: ControlLDM, steps: int, x_T: torch.Tensor, cond: Dict[str, torch.Tensor],
                      noise: torch.Tensor, use_graph: bool = True, uncond: Optional[Dict[str, torch.Tensor]] = None,
-                     cfg_scale: float = 1.0):
+                     cfg_scale: float = 1.0, tiled: bool = False, tile_size: int = -1, tile_stride: int = -1):
         """The fused loop of `sample`, one step per launch, recording per step (x_t, v, x0_hat) with
         x0_hat = _predict_xstart_from_v (spaced_sampler.py:141-147): parity instrumentation for the
         per-step check against the oracle (same kernels and graph as `sample`).  With `uncond` and
-        `cfg_scale != 1` the guided fused loop is traced; v is then the guided v."""
-        if self._guided(uncond, cfg_scale):
+        `cfg_scale != 1` the guided fused loop is traced; v is then the guided v.  With `tiled` the whole-latent
+        loop is traced (one launch = one step of all its chunks); v is the blended v."""
+        self.last_tiling = None
+        if tiled:
+            guided = self._guided(uncond, cfg_scale)
+            self._plan_tiled(model, x_T, cond, uncond, guided, tile_size, tile_stride)
+            self._setup(model, steps, x_T, cond, noise, uncond if guided else None,
+                        self._guidance_scales(cfg_scale, steps) if guided else None, tile_stride=tile_stride)
+        elif self._guided(uncond, cfg_scale):
             if 2 * x_T.shape[0] > model.max_batch:
                 raise ValueError(f"guided sample_trace: batch {x_T.shape[0]} needs max_batch >= {2 * x_T.shape[0]}")
             self._setup(model, steps, x_T, cond, noise, uncond, self._guidance_scales(cfg_scale, steps))
@@ -206,11 +259,13 @@ class SpacedSampler:
                x_T: Optional[torch.Tensor] = None, progress: bool = False, cfg=None,
                noise: Optional[torch.Tensor] = None, use_graph: bool = True):
         """spaced_sampler.py:191-243 -> (x_0, sampled_unet_feats)."""
-        if tiled:
-            raise NotImplementedError("latent tiling is out of scope (SURVEY §2)")
         if x_T is None:
             x_T = torch.randn(x_size, device=device, dtype=torch.float32)
         guided = self._guided(uncond, cfg_scale)
+        self.last_tiling = None
+        if tiled:
+            return self._sample_tiled(model, steps, x_T, cond, uncond if guided else None, cfg_scale, tile_size,
+                                      tile_stride, cfg, noise, use_graph)
         self.last_guided_fused = (2 * x_T.shape[0] <= model.max_batch) if guided else None
         if guided and not self.last_guided_fused:  # no room for 2B rows: two eager forwards per step on the host
             return self._sample_cfg(model, steps, x_T, cond, uncond, cfg_scale, noise)
@@ -238,6 +293,27 @@ class SpacedSampler:
         x, _ = self._get(model, tuple(x_T.shape), dev, False)
         _check_device_faults(dev, "SpacedSampler.sample")
         return x, sampled
+
+    def _sample_tiled(self, model, steps, x_T, cond, uncond, cfg_scale, tile_size, tile_stride, cfg, noise, use_graph):
+        """`sample(tiled=True)`: the fused tiled loop (tair_sampler_prepare_tiled); guidance, when asked for, is
+        always in the chunk graph (each chunk runs its cond rows, then its uncond rows)."""
+        guided = uncond is not None
+        try:
+            feat_steps = list(cfg.exp_args["unet_feat_sampling_timestep"]) if cfg is not None else []
+        except (AttributeError, KeyError, TypeError):
+            feat_steps = []
+        if feat_steps:
+            raise ValueError("tiled sampling has no decoder features: unet_feat_sampling_timestep (feature steps) "
+                             "cannot be combined with tiled=True")
+        self._plan_tiled(model, x_T, cond, uncond, guided, tile_size, tile_stride)
+        self.last_guided_fused = True if guided else None
+        self._setup(model, steps, x_T, cond, noise, uncond, self._guidance_scales(cfg_scale, steps) if guided else None,
+                    tile_stride=tile_stride)
+        dev = x_T.device
+        self._run(model, steps, use_graph, dev)
+        x, _ = self._get(model, tuple(x_T.shape), dev, False)
+        _check_device_faults(dev, "SpacedSampler.sample(tiled)")
+        return x, []
 
     @torch.no_grad()
     def val_sample(self, model: ControlLDM, device, steps: int, x_size: Tuple[int, ...],
@@ -331,6 +407,52 @@ class SpacedSampler:
             vu, _ = model.forward(x, mt, uncond, want_feats=False)
             v = vu + s * (vc - vu)
             if self.parameterization == "eps":  # spaced_sampler.py:133-139
+                x0 = tab["sqrt_recip_alphas_cumprod"][t] * x - tab["sqrt_recipm1_alphas_cumprod"][t] * v
+            else:
+                x0 = tab["sqrt_alphas_cumprod"][t] * x - tab["sqrt_one_minus_alphas_cumprod"][t] * v
+            mean = tab["posterior_mean_coef1"][t] * x0 + tab["posterior_mean_coef2"][t] * x
+            x = mean + (1.0 if t != 0 else 0.0) * torch.sqrt(tab["posterior_variance"][t]) * noise[i]
+        return x, []
+
+    # latent tiling on the host (one eager forward per chunk, torch blending): the baseline tools/tiled_bench.py
+    # measures the fused tiled path against; nothing calls it by default
+    @torch.no_grad()
+    def _sample_tiled_host(self, model, steps, x_T, cond, uncond, cfg_scale, tile_size, tile_stride, noise):
+        guided = self._guided(uncond, cfg_scale)
+        plan = self._plan_tiled(model, x_T, cond, uncond, guided, tile_size, tile_stride)
+        self.make_schedule(steps)
+        dev = x_T.device
+        tab = {k: torch.from_numpy(v).to(dev) for k, v in self.tables.items()}
+        if noise is None:
+            noise = torch.randn((steps,) + tuple(x_T.shape), device=dev)
+        x = x_T.float()
+        B = x.shape[0]
+        w = torch.from_numpy(gaussian_weights(tile_size, tile_size)).to(device=dev, dtype=torch.float32)
+        jobs = [(b, win) for b in range(B) for win in plan["windows"]]
+        rpc = plan["rows_per_chunk"]
+
+        def blended(c, mt_val):
+            acc, cnt = torch.zeros_like(x), torch.zeros_like(x)
+            for j0 in range(0, len(jobs), rpc):
+                part = jobs[j0:j0 + rpc]
+                xin = torch.stack([x[b, :, y0:y1, x0:x1] for b, (y0, y1, x0, x1) in part])
+                cc = {"c_txt": c["c_txt"]}
+                if c.get("c_img") is not None:
+                    cc["c_img"] = torch.stack([c["c_img"][b, :, y0:y1, x0:x1] for b, (y0, y1, x0, x1) in part])
+                mt = torch.full((len(part),), mt_val, device=dev, dtype=torch.long)
+                v, _ = model.forward(xin, mt, cc, want_feats=False)
+                for k, (b, (y0, y1, x0, x1)) in enumerate(part):
+                    acc[b, :, y0:y1, x0:x1] += v[k] * w
+                    cnt[b, :, y0:y1, x0:x1] += w
+            return acc / cnt
+
+        for i, cur in enumerate(np.flip(self.timesteps)):
+            t = steps - i - 1
+            v = blended(cond, int(cur))
+            if guided:
+                vu = blended(uncond, int(cur))
+                v = vu + self.get_cfg_scale(cfg_scale, int(cur)) * (v - vu)
+            if self.parameterization == "eps":
                 x0 = tab["sqrt_recip_alphas_cumprod"][t] * x - tab["sqrt_recipm1_alphas_cumprod"][t] * v
             else:
                 x0 = tab["sqrt_alphas_cumprod"][t] * x - tab["sqrt_one_minus_alphas_cumprod"][t] * v

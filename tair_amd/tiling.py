@@ -7,11 +7,14 @@
   The reference hard-codes the LQ stride 112 / patch 128 (val_patches.py:134-138); they are parameters
   here with the same defaults.  Its host restatement (the checker) is oracle/merge_ref.py.
 * ``split_nonoverlap``: floor(W/tile) x floor(H/tile) crops in raster order (image_splitter.py:23-51).
+* ``sliding_windows`` / ``gaussian_weights`` / ``plan_latent_tiles``: the host plan of latent tiling inside the
+  sampling loop (utils/common.py:125-234 make_tiled_fn): overlapping windows of the whole latent, Gaussian
+  blend weights, and the split of the B x T window rows into equal chunks of at most the handle's batch.
 """
 from __future__ import annotations
 
 import math
-from typing import List, Sequence, Tuple
+from typing import Dict, List, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -117,3 +120,50 @@ def stitch_images(tiles: torch.Tensor, n_images: int, lq_hw: Tuple[int, int], sp
             outs.append(merge_patches_with_overlap_device(t, lq_hw, patch_size=4 * tile, overlap=4 * overlap,
                                                           lq_patch=tile, lq_overlap=overlap))
     return torch.cat(outs)
+
+
+# ---------------------------------------------------------------------------------------------------
+# latent tiling inside the sampling loop (utils/common.py:125-234)
+# ---------------------------------------------------------------------------------------------------
+def _starts(n: int, size: int, stride: int) -> List[int]:
+    out = list(range(0, n - size + 1, stride))
+    if (n - size) % stride != 0:  # the last window is appended flush with the edge
+        out.append(n - size)
+    return out
+
+
+def sliding_windows(h: int, w: int, size: int, stride: int) -> List[Tuple[int, int, int, int]]:
+    """utils/common.py:125-140: (y0, y1, x0, x1) of every size x size window, row-major."""
+    return [(y, y + size, x, x + size) for y in _starts(h, size, stride) for x in _starts(w, size, stride)]
+
+
+def gaussian_weights(tile_width: int, tile_height: int) -> np.ndarray:
+    """utils/common.py:144-171: float64 [tile_height, tile_width] blend weights, var = 0.01.  The column
+    midpoint is (width - 1) / 2 and the row midpoint height / 2: the reference's asymmetry is kept."""
+    var = 0.01
+    norm = np.sqrt(2 * np.pi * var)
+    mx = (tile_width - 1) / 2
+    xp = [np.exp(-(x - mx) * (x - mx) / (tile_width * tile_width) / (2 * var)) / norm for x in range(tile_width)]
+    my = tile_height / 2
+    yp = [np.exp(-(y - my) * (y - my) / (tile_height * tile_height) / (2 * var)) / norm for y in range(tile_height)]
+    return np.outer(yp, xp)
+
+
+def plan_latent_tiles(B: int, H: int, W: int, size: int, stride: int, max_batch: int, guided: bool) -> Dict:
+    """The rows one tiled sampler step runs: N = B * T window rows (image-major, then window order) in
+    n_chunks forwards of rows_per_chunk rows each (x 2 when guided: cond rows, then uncond rows).  All chunks
+    have the same row count, so the network runs at one batch size with one set of plans; the `pad` unused
+    rows of the last chunk repeat the job's last window and are never blended."""
+    if stride < 1:
+        raise ValueError(f"tile stride {stride} must be >= 1")
+    if H < size or W < size:
+        raise ValueError(f"latent {H}x{W} is smaller than the tile {size}")
+    cap = max_batch // 2 if guided else max_batch
+    if cap < 1:
+        raise ValueError(f"max_batch {max_batch} leaves no room for a {'guided ' if guided else ''}window row")
+    windows = sliding_windows(H, W, size, stride)
+    n = B * len(windows)
+    n_chunks = -(-n // cap)
+    rows_per_chunk = -(-n // n_chunks)
+    return dict(windows=windows, rows=n, cap=cap, n_chunks=n_chunks, rows_per_chunk=rows_per_chunk,
+                pad=n_chunks * rows_per_chunk - n)
