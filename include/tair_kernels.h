@@ -240,6 +240,23 @@ int tair_k_gn_apply_stats(const void* x, int ldx, int x_lo, int B, int HW, int C
 int tair_k_softmax_split(const float* S, int lds, int rows, int L, void* P, void* stream);
 /* [B][L][3C] (hi, lo, hi) -> [B][C][3L] (hi, hi, lo): the V^T operand of P.V. */
 int tair_k_transpose_split(const void* x, int B, int L, int C, void* y, void* stream);
+/* The two above for a token count L that is no multiple of 64 (the tiles of the tiled VAE, tilevae.py:307-579:
+ * 30x30, 30x24, ... latent): the planes are Lp columns wide (Lp >= L, Lp % 64 == 0), P [rows][3 Lp] and
+ * y [B][C][3 Lp], with zeros at columns L..Lp of every plane, so P.V runs as a GEMM over K = 3 Lp and the padded
+ * keys contribute exactly zero.  Columns L.. of S are never read.  Bad arguments: -1 with a message, no launch. */
+int tair_k_softmax_split_pad(const float* S, int lds, int rows, int L, int Lp, void* P, void* stream);
+int tair_k_transpose_split_pad(const void* x, int B, int L, int Lp, int C, void* y, void* stream);
+/* Cross-tile GroupNorm of the tiled VAE (tilevae.py:232-278 GroupNormParam.summary).  slots: T statistics slots
+ * in the st_acc layout (8 replicas st_rs doubles apart, (b * G + g) * 2 = (sum x, sum x^2)), slot t at
+ * slots + t * slot_stride doubles, filled by the GEMM that produced tile t: pixels[t] (host array) pixels per
+ * image, groups of cg channels.  Per (b, g) in fp64: mean_t, var_t = max(sum x^2 / cnt_t - mean_t^2, 0) with
+ * cnt_t = pixels[t] * cg; mean = sum_t w_t mean_t, var = sum_t w_t var_t, w_t = pixels[t] / sum pixels (the
+ * reference's weighted average of variances, not the union's variance); every slot is rewritten as replica 0 =
+ * (mean cnt_t, (var + mean^2) cnt_t), replicas 1-7 = 0, so tair_k_gn_apply_stats with that tile's own HW
+ * normalises with the merged pair.  T <= 256.  Bad arguments (T < 1, B < 1, a pixel count < 1, null pointers,
+ * st_rs < 2 B G, overlapping slots): -1 with a message, before any launch. */
+int tair_k_gn_stats_merge(double* slots, int64_t slot_stride, int T, const int* pixels, int B, int G, int cg,
+                          int st_rs, void* stream);
 /* Multi-scale deformable attention sampling of the stage-3 TESTR spotter, replacing the reference's
  * MSDeformAttnFunction / ms_deformable_im2col_gpu_kernel (testr/adet/layers/ms_deform_attn.py:19-37,
  * csrc/DeformAttn/ms_deform_im2col_cuda.cuh:238-299): fp32 value (N, S, M, D), level shapes

@@ -312,14 +312,24 @@ class ControlLDM:
         return f.value
 
     # ------------------------------------------------------------------ VAE / condition
+    # the tiled VAE is built (cldm.py:92-141 with tiled=True; Pipeline.apply_cldm checks this before it passes
+    # vae_encoder_tiled / vae_decoder_tiled on)
+    vae_tiling = True
+
     @torch.no_grad()
     def vae_encode(self, image: torch.Tensor, sample: bool = True, tiled: bool = False, tile_size: int = -1):
         """cldm.py:92-119.  The posterior mode (sample=False, prepare_condition's c_img) runs on the HIP
         split-precision encoder (vae_backend "hip"); sampling keeps the stock-torch encoder (it needs the
-        log-variance half of the moments and a generator)."""
+        log-variance half of the moments and a generator).  tiled: the reference's tiled VAE with fast mode off
+        (tile_size in image pixels; an image of at most 64 + tile_size per side runs untiled)."""
         if tiled:
-            raise NotImplementedError("tiled VAE is out of scope (SURVEY §2)")
-        if not sample and self.vae_backend == "hip":
+            if not sample and self.vae_backend == "hip":
+                z = self.hip_vae_encoder().encode_mode_tiled(image, tile_size)
+            elif not sample:
+                z = self.vae.encode_mode_tiled(image, tile_size)
+            else:
+                z = self.vae.encode_sample_tiled(image, tile_size)
+        elif not sample and self.vae_backend == "hip":
             z = self.hip_vae_encoder().encode_mode(image)
         else:
             z = self.vae.encode_mode(image) if not sample else self.vae.encode_sample(image)
@@ -327,8 +337,12 @@ class ControlLDM:
 
     @torch.no_grad()
     def vae_decode(self, z: torch.Tensor, tiled: bool = False, tile_size: int = -1) -> torch.Tensor:
+        """cldm.py:121-141.  tiled: the reference's tiled VAE with fast mode off (tile_size in latent pixels; a
+        latent of at most 22 + tile_size per side runs untiled)."""
         if tiled:
-            raise NotImplementedError("tiled VAE is out of scope (SURVEY §2)")
+            if self.vae_backend == "hip":
+                return self.hip_vae().decode_tiled(z.float() / self.scale_factor, tile_size)
+            return self.vae.decode_tiled(z / self.scale_factor, tile_size)
         if self.vae_backend == "hip":
             return self.hip_vae().decode(z.float() / self.scale_factor)
         return self.vae.decode(z / self.scale_factor)
@@ -357,7 +371,8 @@ class ControlLDM:
             if self.clip is None:
                 raise NotImplementedError("CLIP text encoder not built: pass c_txt explicitly")
             c_txt = self.clip.encode(txt)
-        return dict(c_txt=c_txt, c_img=self.vae_encode(cond_img * 2 - 1, sample=False))
+        return dict(c_txt=c_txt, c_img=self.vae_encode(cond_img * 2 - 1, sample=False, tiled=tiled,
+                                                       tile_size=tile_size))
 
 
 # ---------------------------------------------------------------------------------------------

@@ -658,8 +658,10 @@ hipError_t gemm_grouped(const GemmArgs* args, int n, hipStream_t s) {
     // the split was planned for the wider tile: a grid that the smaller tile now fills no longer needs it (B = 64
     // 8x8-level convs: 128x320/s2 -> 64x128, whose 640 tiles ran with fp32 slabs and a combine for nothing)
     if (TAIR_BATCH_XCD && splits > 1 && kern == GEMM_KERN_TILE && (long)cdiv(a.M, abm) * cdiv(a.N, bn) >= 512) splits = 1;
-    if (st_hw % abm) {
-      set_error("gemm: GroupNorm statistics need hw %% 64 == 0 (hw %d)", st_hw);
+    // (one batch element, M == hw: no tile can straddle two, and rows past M take no part in the sums -- the
+    // tiles of the tiled VAE, e.g. 30 x 30 pixels)
+    if (st_hw % abm && a.M != st_hw) {
+      set_error("gemm: GroupNorm statistics over several batch elements need hw %% 64 == 0 (hw %d)", st_hw);
       return hipErrorInvalidValue;
     }
     for (int i = 0; i < n; ++i)

@@ -284,6 +284,43 @@ int tair_k_transpose_split(const void* x, int B, int L, int C, void* y, void* st
   return transpose_split((const bf16*)x, B, L, C, (bf16*)y, (hipStream_t)stream) == hipSuccess ? 0 : -2;
 }
 
+int tair_k_softmax_split_pad(const float* S, int lds, int rows, int L, int Lp, void* P, void* stream) {
+  const hipError_t e = softmax_split_pad(S, lds, rows, L, Lp, (bf16*)P, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) {
+    set_error("softmax_split_pad: bad arguments (lds %d, rows %d, L %d, Lp %d)", lds, rows, L, Lp);
+    return -1;
+  }
+  return e == hipSuccess ? 0 : -2;
+}
+
+int tair_k_transpose_split_pad(const void* x, int B, int L, int Lp, int C, void* y, void* stream) {
+  const hipError_t e = transpose_split_pad((const bf16*)x, B, L, Lp, C, (bf16*)y, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) {
+    set_error("transpose_split_pad: bad arguments (B %d, L %d, Lp %d, C %d)", B, L, Lp, C);
+    return -1;
+  }
+  return e == hipSuccess ? 0 : -2;
+}
+
+int tair_k_gn_stats_merge(double* slots, int64_t slot_stride, int T, const int* pixels, int B, int G, int cg,
+                          int st_rs, void* stream) {
+  GnMergeArgs a{};
+  a.slots = slots; a.slot_stride = slot_stride;
+  a.T = T; a.B = B; a.G = G; a.cg = cg; a.st_rs = st_rs;
+  hipError_t e = hipErrorInvalidValue;
+  if (pixels && T >= 1 && T <= GN_MERGE_MAX_TILES) {
+    for (int t = 0; t < T; ++t) a.pixels[t] = pixels[t];
+    e = gn_stats_merge(a, (hipStream_t)stream);
+  }
+  if (e == hipErrorInvalidValue) {
+    set_error("gn_stats_merge: bad arguments (slots %p, slot_stride %lld, T %d (1..%d), pixel counts %s, B %d, G %d, "
+              "cg %d, st_rs %d)", (void*)slots, (long long)slot_stride, T, GN_MERGE_MAX_TILES,
+              pixels ? "must be >= 1" : "null", B, G, cg, st_rs);
+    return -1;
+  }
+  return e == hipSuccess ? 0 : -2;
+}
+
 int tair_k_ms_deform_attn(const float* value, int N, int S, int M, int D, const int* level_hw, int L, int Q, int P,
                           const float* loc, const float* attn, float* out, void* stream) {
   if (!level_hw || L < 1 || L > MSDA_MAX_LEVELS) {

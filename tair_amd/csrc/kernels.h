@@ -231,6 +231,22 @@ hipError_t groupnorm_apply_grouped(const GnArgs* a, int n, int B, int HW, int C,
 hipError_t softmax_split(const float* S, int lds, int rows, int L, bf16* P, hipStream_t s);
 // [B][L][3C] activation-order planes -> [B][C][3L] weight-order planes (hi, hi, lo): V -> V^T operand
 hipError_t transpose_split(const bf16* x, int B, int L, int C, bf16* y, hipStream_t s);
+// The same two for a token count L that is no multiple of 64 (tiles of the tiled VAE): planes of Lp = roundup(L, 64)
+// columns, P [rows][3 Lp] and y [B][C][3 Lp], zero at columns L..Lp (the reduction of P.V then runs over 3 Lp and
+// the padded keys add exactly nothing); hipErrorInvalidValue for Lp < L or Lp % 64
+hipError_t softmax_split_pad(const float* S, int lds, int rows, int L, int Lp, bf16* P, hipStream_t s);
+hipError_t transpose_split_pad(const bf16* x, int B, int L, int Lp, int C, bf16* y, hipStream_t s);
+// Cross-tile GroupNorm statistics of the tiled VAE: T slots in the StatTgt layout, slot_stride doubles apart, each
+// with the (sum, sum^2) of one tile of pixels[t] pixels per image (groups of cg channels).  Per (image, group):
+// mean = sum_t w_t mean_t, var = sum_t w_t var_t (biased, clamped at 0), w_t = pixels[t] / sum pixels; every slot
+// is rewritten as replica 0 = (mean cnt_t, (var + mean^2) cnt_t), replicas 1.. = 0, cnt_t = pixels[t] cg.
+constexpr int GN_MERGE_MAX_TILES = 256;
+struct GnMergeArgs {
+  double* slots; long long slot_stride;
+  int T, B, G, cg, st_rs;
+  int pixels[GN_MERGE_MAX_TILES];
+};
+hipError_t gn_stats_merge(const GnMergeArgs& a, hipStream_t s);
 // y8 != null: the output goes out as OCP e4m3 instead (the fp8 linears' activation operand, configs[4]):
 // y8[t][c] = e4m3(y[t][c] / s8[t]) with s8[t] = max_c |y[t][c]| / 448 (1 for an all-zero row), bytes
 // C..ld8 of the row zeroed (the GEMM's 128-value K-tiles); y may then be null
