@@ -74,12 +74,15 @@ typedef struct {
 } tair_gemm_desc;
 
 /* act: 0 none, 1 SiLU, 2 GEGLU — output channels packed as (x_2q, x_2q+1, gate_2q, gate_2q+1) groups,
- * y[:, 2q+i] = x_2q+i * gelu(gate_2q+i) written to out (N/2 bf16 columns).
+ * y[:, 2q+i] = x_2q+i * gelu(gate_2q+i) written to out (N/2 bf16 columns); 3 GELU, y = gelu_erf(alpha acc + bias
+ * [+ res]) (nn.GELU of the CLIP text tower's MLP, open_clip transformer.py:199-256): dense bf16 GEMMs on the
+ * <= 128 x 128 tile kernels, split-K included; a plan that does not carry it is refused.  Any other act: error.
  * nn.Linear / nn.Conv2d (3x3 pad 1, stride 1|2, nearest-x2 upsample fused) + bias + time-emb +
  * residual epilogue (unet.py:51-223, attention.py:19-353). */
 int tair_k_gemm(const tair_gemm_desc* d, void* stream);
 /* Faults the GEMM kernels detected on the current device since the last reset (a cooperative split-K slice
- * that gave up waiting for its tile's other slices, so its sums are incomplete): *count receives the number;
+ * that gave up waiting for its tile's other slices, so its sums are incomplete; a token id outside the embedding
+ * table that tair_k_embed_tokens clamped): *count receives the number;
  * reset != 0 clears it.  Synchronous (reads one device int): call after the work is synchronised, outside
  * stream capture.  A non-zero count means the results of that work are invalid. */
 int tair_fault_count(int reset, int* count);
@@ -114,6 +117,20 @@ int tair_k_attention_ex(const void* q, int ldq, const void* k, int ldk, const vo
 int tair_k_attention_tk(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo,
                         int B, int H, int Sq, int Skv, int kv_bstride, float scale, void* ws, int64_t ws_bytes,
                         int* tickets, int tickets_cap, int force_qsets, int force_splits, void* stream);
+/* softmax(Q K^T * scale + causal mask) V, head dim 64: the text tower's self-attention (open_clip
+ * transformer.py:199-256 with the additive mask of build_attention_mask, :589-595: query i sees keys 0..i; no
+ * padding mask).  Rows b * S + i of q / k / v / o, head h at columns h * 64 (operands may be strided out of one
+ * fused [T, 3C] q|k|v buffer; leading dimensions % 8 == 0, 16-byte aligned pointers), bf16 in and out, 1 <= S <= 128.
+ * One workgroup per (batch, head, 64-query block) stages its keys once in the LDS; a wave owns 16 queries and skips
+ * the key tiles wholly above its diagonal.  Bad arguments: -1 with a message, before any launch. */
+int tair_k_attention_causal(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo,
+                            int B, int H, int S, float scale, void* stream);
+/* x = token_embedding[id] + positional_embedding in fp32 (clip.py:38-39), written as
+ * two bf16 planes: hi = bf16(x) at out_hi[(b * L + l) * ld + c], lo = bf16(x - hi) out_lo_offset elements further
+ * on.  ids [B * L] int64 on the device (capturable); table [vocab][C], pos [L][C] fp32; C % 4 == 0.  An id outside
+ * [0, vocab) is clamped into the table and counted in the fault counter (tair_fault_count). */
+int tair_k_embed_tokens(const void* ids, int B, int L, const float* table, int vocab, const float* pos, int C,
+                        void* out_hi, int out_lo_offset, int ld, void* stream);
 /* GroupNorm(G, eps) [+ SiLU] on NHWC bf16 (util.py:191-193, attention.py:48-51). ss: [B][C][2] fp32,
  * ws: [B*G*64*2] fp32 scratch. */
 int tair_k_groupnorm(const void* x, int ldx, int B, int HW, int C, int G, float eps, const float* gamma,
@@ -125,6 +142,12 @@ int tair_k_groupnorm_ex(const void* x, int ldx, int B, int HW, int C, int G, flo
 /* LayerNorm over C (attention.py:255-257). */
 int tair_k_layernorm(const void* x, int T, int C, const float* gamma, const float* beta, float eps, void* y,
                      void* stream);
+/* LayerNorm over C of a two-plane residual stream (the text tower's ln_1 / ln_2 / ln_final, open_clip
+ * transformer.py:199-256, clip.py:43): x = x[t * ldx + c] + x[t * ldx + x_lo + c] (x_lo = 0: one plane), statistics
+ * and apply in fp32; out_f32 0 writes bf16 rows (the next GEMM's operand), 1 fp32 rows (ln_final: the context the
+ * sampler takes), row stride ldy elements.  C % 8 == 0, C <= 2560. */
+int tair_k_layernorm_split(const void* x, int ldx, int x_lo, int T, int C, const float* gamma, const float* beta,
+                           float eps, void* y, int ldy, int out_f32, void* stream);
 /* LayerNorm over C with e4m3 output for the fp8 linears (configs[4]): y8 [T][ld8] bytes (OCP e4m3,
  * bytes C..ld8 zeroed), s8 [T] per-token scale (max |y| / 448): y ~= y8 * s8. */
 int tair_k_layernorm_fp8(const void* x, int T, int C, const float* gamma, const float* beta, float eps, void* y8,

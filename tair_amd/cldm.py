@@ -83,7 +83,9 @@ class ControlLDM:
                  clip_cfg: Optional[dict] = None, controlnet_cfg: Optional[dict] = None,
                  latent_scale_factor: float = 0.18215, *, max_batch: int = 1,
                  latent_hw: Tuple[int, int] = (64, 64), device="cuda", with_vae: bool = True,
-                 fp8: bool = False):
+                 fp8: bool = False, clip_backend: str = "torch"):
+        if clip_backend not in ("torch", "hip"):
+            raise ValueError(f"clip_backend must be 'torch' or 'hip', got {clip_backend!r}")
         self.device = torch.device(device)
         if self.device.type != "cuda" or not torch.cuda.is_available():
             raise _lib.TairError("tair_amd.ControlLDM needs a ROCm GPU (no CPU fallback)")
@@ -114,11 +116,13 @@ class ControlLDM:
             from .vae import AutoencoderKL
             ddcfg = (vae_cfg or {}).get("ddconfig", {}) if vae_cfg else {}
             self.vae = AutoencoderKL(embed_dim=(vae_cfg or {}).get("embed_dim", 4), **ddcfg).to(self.device).eval()
-        # CLIP-H text tower (clip_cfg): stock PyTorch-ROCm, outside the HIP hot path
+        # CLIP-H text tower (clip_cfg): clip_backend "torch" = stock PyTorch-ROCm (the default), "hip" = the
+        # tower on the HIP kernels (tair_amd/clip_hip.py: stage 3 re-encodes the prompt every sampler step)
         self.clip = None
+        self.clip_backend = clip_backend
         if clip_cfg:
-            from .clip import FrozenOpenCLIPEmbedder
-            self.clip = FrozenOpenCLIPEmbedder(**clip_cfg).to(self.device).eval()
+            from .clip_hip import build_text_tower
+            self.clip = build_text_tower(clip_cfg, clip_backend, device=self.device, max_batch=max(8, max_batch))
         # host references of the loaded unet.* tensors, for load_controlnet_from_unet (cldm.py:68-90);
         # dropped at finalize() so a loaded model does not pin ~3.5 GB of fp32 state per process
         self._host_unet: Dict[str, torch.Tensor] = {}
@@ -212,7 +216,7 @@ class ControlLDM:
         if self.clip is not None:
             clip_sd = {k[len("cond_stage_model."):]: v for k, v in sd.items() if k.startswith("cond_stage_model.")}
             if clip_sd:
-                own = set(self.clip.state_dict())
+                own = self.clip.reference_keys() if hasattr(self.clip, "reference_keys") else set(self.clip.state_dict())
                 self.clip.load_state_dict({k: v for k, v in clip_sd.items() if k in own}, strict=False)
                 used.update("cond_stage_model." + k for k in clip_sd if k in own)
         unused = set(sd.keys()) - used

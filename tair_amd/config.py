@@ -57,7 +57,7 @@ def diffusion_params(cfg: Dict[str, Any]) -> Dict[str, Any]:
 
 
 def build_model(cfg: Dict[str, Any], *, max_batch: int = 1, latent_hw: Tuple[int, int] = (64, 64), device="cuda",
-                with_clip: bool = True):
+                with_clip: bool = True, clip_backend: str = "torch"):
     """ControlLDM(**cfg.model.cldm.params) on the HIP runtime (initialize.py:85)."""
     from .cldm import ControlLDM
     p = cldm_params(cfg)
@@ -67,7 +67,7 @@ def build_model(cfg: Dict[str, Any], *, max_batch: int = 1, latent_hw: Tuple[int
         unet_cfg["hint_channels"] = cn["hint_channels"]
     return ControlLDM(unet_cfg=unet_cfg, vae_cfg=p.get("vae_cfg"), clip_cfg=p.get("clip_cfg") if with_clip else None,
                       controlnet_cfg=cn, latent_scale_factor=p.get("latent_scale_factor", 0.18215),
-                      max_batch=max_batch, latent_hw=latent_hw, device=device)
+                      max_batch=max_batch, latent_hw=latent_hw, device=device, clip_backend=clip_backend)
 
 
 def build_diffusion(cfg: Dict[str, Any]):

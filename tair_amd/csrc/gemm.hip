@@ -97,6 +97,7 @@ static int* fault_word() {
   if (hipGetDevice(&dev) != hipSuccess || dev < 0 || dev >= 16) return nullptr;
   return g_fault[dev];
 }
+int* gemm_fault_word() { return fault_word(); }
 
 hipError_t gemm_fault_count(int* count, bool reset) {
   *count = 0;
@@ -533,6 +534,15 @@ hipError_t gemm_grouped(const GemmArgs* args, int n, hipStream_t s) {
     set_error("gemm: K=%d not a multiple of %d", a.K, kq);
     return hipErrorInvalidValue;
   }
+  if (a.act < 0 || a.act > 3) {
+    set_error("gemm: act %d (0 none, 1 SiLU, 2 GEGLU, 3 GELU)", a.act);
+    return hipErrorInvalidValue;
+  }
+  // GELU (nn.GELU of the CLIP text tower's MLP, transformer.py:199-256): the dense bf16 linears only
+  if (a.act == 3 && (a.amode != A_DENSE || a.f8 || a.out_split || a.st[0].acc || a.rst || a.gn_st)) {
+    set_error("gemm: the GELU epilogue takes a dense bf16 GEMM without split planes or statistics targets");
+    return hipErrorInvalidValue;
+  }
   if (a.out_split && (a.act == 2 || a.out_f32 || a.ldo < 3 * a.N)) {
     set_error("gemm: split output needs a plain epilogue and ldo >= 3N (N=%d, ldo=%d)", a.N, a.ldo);
     return hipErrorInvalidValue;
@@ -801,6 +811,13 @@ hipError_t gemm_grouped(const GemmArgs* args, int n, hipStream_t s) {
   if (a.rst && splits > 1 && !ink) splits = 1;  // row statistics need the final values: no K split then
   if (a.rst && (kern == GEMM_KERN_PHASE || (bm < 0 ? -bm : bm) > 128 || (splits > 1 && !ink))) {
     set_error("gemm: LayerNorm row statistics need a <= 128-row tile plan (got %dx%d, %d splits)", bm, bn, splits);
+    return hipErrorInvalidValue;
+  }
+  // GELU is carried by the LDS-staged generic epilogue and the split-K reduce of the <= 128 x 128 tile kernels
+  // (what the planner picks for the text tower's M = 77 ... 616); any other plan refuses instead of skipping it
+  if (a.act == 3 && !((kern == GEMM_KERN_TILE || kern == GEMM_KERN_SHALLOW || kern == GEMM_KERN_DEEP ||
+                       kern == GEMM_KERN_KGROUP) && bm > 0 && bm <= 128 && bn <= 128)) {
+    set_error("gemm: the GELU epilogue is not built for tile %dx%d of kernel %d", bm, bn, kern);
     return hipErrorInvalidValue;
   }
   GemmGroup P;

@@ -501,6 +501,10 @@ TAIR_DEV void epilogue4(const PA& p, int m, int n, f32x4 acc, float (&stored)[4]
 #pragma unroll
       for (int r = 0; r < 4; ++r) v[r] = silu_f(v[r]);
     }
+    if (p.act == 3) {  // nn.GELU (erf form)
+#pragma unroll
+      for (int r = 0; r < 4; ++r) v[r] = gelu_erf(v[r]);
+    }
   } else {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
@@ -513,6 +517,7 @@ TAIR_DEV void epilogue4(const PA& p, int m, int n, f32x4 acc, float (&stored)[4]
         v[r] += p.res_lo ? bf2f(rp[0]) + bf2f(rp[p.res_lo]) : bf2f(rp[0]);
       }
       if (p.act == 1) v[r] = silu_f(v[r]);
+      if (p.act == 3) v[r] = gelu_erf(v[r]);
     }
   }
   if (p.act == 2) {  // GEGLU pair (x_2q, x_2q+1, gate_2q, gate_2q+1) -> out columns 2q, 2q+1 (N % 4 == 0)
@@ -802,6 +807,10 @@ TAIR_DEV void epilogue8(const PA& p, int m, int n, bool vec_rt, const EpiIn& in,
   if (TAIR_EH(F, E_SILU, p.act == 1)) {
 #pragma unroll
     for (int e = 0; e < 8; ++e) v[e] = silu_f(v[e]);
+  }
+  if (GEN && p.act == 3) {  // nn.GELU (erf form; the generic loop only: epi_mask lists no set for it)
+#pragma unroll
+    for (int e = 0; e < 8; ++e) v[e] = gelu_erf(v[e]);
   }
 #pragma unroll
   for (int e = 0; e < 8; ++e) stored[e] = 0.f;

@@ -107,6 +107,37 @@ int tair_k_attention_tk(const void* q, int ldq, const void* k, int ldk, const vo
                  hipSuccess ? 0 : -2;
 }
 
+int tair_k_attention_causal(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo,
+                            int B, int H, int S, float scale, void* stream) {
+  const hipError_t e = attention_causal((const bf16*)q, ldq, (const bf16*)k, ldk, (const bf16*)v, ldv, (bf16*)o, ldo, B,
+                                        H, S, scale, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) {
+    set_error("attention_causal: bad arguments (B %d, H %d, S %d (1..%d), scale %g, ld %d / %d / %d / %d: %% 8 and "
+              ">= 64 H, 16-byte aligned pointers)", B, H, S, CAUSAL_MAX_S, (double)scale, ldq, ldk, ldv, ldo);
+    return -1;
+  }
+  return e == hipSuccess ? 0 : -2;
+}
+
+int tair_k_embed_tokens(const void* ids, int B, int L, const float* table, int vocab, const float* pos, int C,
+                        void* out_hi, int out_lo_offset, int ld, void* stream) {
+  const hipError_t e = embed_tokens((const int64_t*)ids, B, L, table, vocab, pos, C, (bf16*)out_hi, out_lo_offset, ld,
+                                    (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) {
+    set_error("embed_tokens: bad arguments (B %d, L %d, vocab %d, C %d (%% 4), lo offset %d (>= C), ld %d)", B, L, vocab,
+              C, out_lo_offset, ld);
+    return -1;
+  }
+  return e == hipSuccess ? 0 : -2;
+}
+
+int tair_k_layernorm_split(const void* x, int ldx, int x_lo, int T, int C, const float* gamma, const float* beta,
+                           float eps, void* y, int ldy, int out_f32, void* stream) {
+  const hipError_t e = layernorm_split((const bf16*)x, ldx, x_lo, T, C, gamma, beta, eps, y, ldy, out_f32,
+                                       (hipStream_t)stream);
+  return e == hipSuccess ? 0 : e == hipErrorInvalidValue ? -1 : -2;
+}
+
 int tair_k_groupnorm(const void* x, int ldx, int B, int HW, int C, int G, float eps, const float* gamma,
                      const float* beta, int silu, void* y, int ldy, float* ss, float* ws, void* stream) {
   hipStream_t s = (hipStream_t)stream;

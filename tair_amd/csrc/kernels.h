@@ -47,7 +47,7 @@ struct GemmArgs {
   // epilogue: v = alpha*acc + (scale_bias ? alpha : 1)*bias + emb + res; v = act(v)
   float alpha;
   int scale_bias;                             // ControlNet zero-conv: (W h + b) * control_scale
-  int act;                                    // 0 none, 1 SiLU, 2 GEGLU pairs (see epilogue4)
+  int act;                                    // 0 none, 1 SiLU, 2 GEGLU pairs (see epilogue4), 3 GELU (erf form)
   const float* bias;                          // [N] or null
   const float* emb; int ld_emb; const int* emb_row;  // + emb[emb_row[b]*ld_emb + n], b = m / (Ho*Wo)
   int rows_per_b;                             // pixels per batch element for emb indexing
@@ -307,6 +307,23 @@ hipError_t attention(const bf16* q, int ldq, const bf16* k, int ldk, const bf16*
                      bf16* o, int ldo, int B, int H, int Sq, int Skv, int kv_bstride,
                      float scale, hipStream_t s, void* ws = nullptr, size_t ws_bytes = 0,
                      int force_qsets = 0, int force_splits = 0);
+
+// ---- CLIP text tower (clip.hip, norm.hip; clip.py:8-61, open_clip transformer.py:199-256) --------
+constexpr int CAUSAL_MAX_S = 128;  // keys of a (batch, head) staged in the LDS at once
+// O = softmax(Q K^T * scale + causal mask) V per (batch, head), d = 64, S <= CAUSAL_MAX_S tokens per batch element
+// (rows b * S + i of q / k / v / o; query i sees keys 0..i); hipErrorInvalidValue for a bad shape, before any launch
+hipError_t attention_causal(const bf16* q, int ldq, const bf16* k, int ldk, const bf16* v, int ldv, bf16* o, int ldo,
+                            int B, int H, int S, float scale, hipStream_t s);
+// x[b * L + l] = table[ids[b * L + l]] + pos[l] in fp32, stored as hi = bf16(x) at out[row * ld + c] and
+// lo = bf16(x - hi) at out[row * ld + out_lo + c]; an id outside [0, vocab) is clamped and counted in the device
+// fault counter (gemm_fault_count)
+hipError_t embed_tokens(const int64_t* ids, int B, int L, const float* table, int vocab, const float* pos, int C,
+                        bf16* out, int out_lo, int ld, hipStream_t s);
+// LayerNorm over C of a two-plane input x = x[t * ldx + c] + x[t * ldx + x_lo + c] (x_lo = 0: one plane) into bf16
+// or fp32 rows of stride ldy
+hipError_t layernorm_split(const bf16* x, int ldx, int x_lo, int T, int C, const float* gamma, const float* beta,
+                           float eps, void* y, int ldy, int out_f32, hipStream_t s);
+int* gemm_fault_word();  // the current device's fault counter (null before gemm_init)
 
 // ---- misc ---------------------------------------------------------------------------------
 hipError_t geglu(const bf16* xg, int T, int D, bf16* y, hipStream_t s);

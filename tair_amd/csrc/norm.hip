@@ -475,7 +475,90 @@ __global__ __launch_bounds__(256) void layernorm_kernel(const LnGroup P, int T, 
   }
 }
 
+// LayerNorm of a two-plane residual stream (the CLIP text tower, clip_hip.py): x = hi + lo (exact in fp32), the
+// layernorm_kernel arithmetic (two-pass variance), bf16 or fp32 rows out.  One wave per token.
+template <int VPL, bool F32>
+__global__ __launch_bounds__(256) void layernorm_split_kernel(const bf16* __restrict__ x, int ldx, int x_lo, int T, int C,
+                                                              const float* __restrict__ gamma,
+                                                              const float* __restrict__ beta, float eps, void* y, int ldy) {
+  const int lane = threadIdx.x & 63;
+  const int t = blockIdx.x * 4 + (threadIdx.x >> 6);
+  if (t >= T) return;
+  const int cv = C / 8;
+  const bf16* xr = x + (size_t)t * ldx;
+  float v[VPL][8];
+  float sum = 0.f;
+#pragma unroll
+  for (int j = 0; j < VPL; ++j) {
+    const int vi = lane + 64 * j;
+    if (vi < cv) {
+      union { uint4 u; bf16 h[8]; } in, il;
+      in.u = *(const uint4*)(xr + vi * 8);
+      il.u = x_lo ? *(const uint4*)(xr + x_lo + vi * 8) : uint4{0u, 0u, 0u, 0u};
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { v[j][e] = bf2f(in.h[e]) + bf2f(il.h[e]); sum += v[j][e]; }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) v[j][e] = 0.f;
+    }
+  }
+  const float mean = wave_sum(sum) / C;
+  float sq = 0.f;
+#pragma unroll
+  for (int j = 0; j < VPL; ++j) {
+    if (lane + 64 * j < cv) {
+#pragma unroll
+      for (int e = 0; e < 8; ++e) { const float d = v[j][e] - mean; sq += d * d; }
+    }
+  }
+  const float rstd = rsqrtf(wave_sum(sq) / C + eps);
+#pragma unroll
+  for (int j = 0; j < VPL; ++j) {
+    const int vi = lane + 64 * j;
+    if (vi < cv) {
+      const float4 g0 = *(const float4*)(gamma + vi * 8), g1 = *(const float4*)(gamma + vi * 8 + 4);
+      const float4 b0 = *(const float4*)(beta + vi * 8), b1 = *(const float4*)(beta + vi * 8 + 4);
+      const float gg[8] = {g0.x, g0.y, g0.z, g0.w, g1.x, g1.y, g1.z, g1.w};
+      const float bb[8] = {b0.x, b0.y, b0.z, b0.w, b1.x, b1.y, b1.z, b1.w};
+      float r[8];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) r[e] = (v[j][e] - mean) * rstd * gg[e] + bb[e];
+      if (F32) {
+        float* yr = (float*)y + (size_t)t * ldy + vi * 8;
+        *(float4*)yr = make_float4(r[0], r[1], r[2], r[3]);
+        *(float4*)(yr + 4) = make_float4(r[4], r[5], r[6], r[7]);
+      } else {
+        union { uint4 u; bf16 h[8]; } out;
+#pragma unroll
+        for (int e = 0; e < 8; ++e) out.h[e] = f2bf(r[e]);
+        *(uint4*)((bf16*)y + (size_t)t * ldy + vi * 8) = out.u;
+      }
+    }
+  }
+}
+
 }  // namespace
+
+hipError_t layernorm_split(const bf16* x, int ldx, int x_lo, int T, int C, const float* gamma, const float* beta,
+                           float eps, void* y, int ldy, int out_f32, hipStream_t s) {
+  const int cv = C / 8;
+  if (!x || !y || !gamma || !beta || T < 1 || C < 8 || (C % 8) || cv > 320 || x_lo < 0 || (x_lo && x_lo < C) ||
+      (x_lo & 7) || ldx < x_lo + C || (ldx & 7) || ldy < C || (ldy & 7) || ((uintptr_t)x & 15) || ((uintptr_t)y & 15) ||
+      ((uintptr_t)gamma & 15) || ((uintptr_t)beta & 15)) {
+    set_error("layernorm_split: bad arguments (T %d, C %d, ldx %d, x_lo %d, ldy %d; C, ldx, x_lo, ldy %% 8, 16-byte "
+              "aligned pointers, C <= 2560)", T, C, ldx, x_lo, ldy);
+    return hipErrorInvalidValue;
+  }
+  const dim3 grid(cdiv(T, 4));
+  using LnsFn = void (*)(const bf16*, int, int, int, int, const float*, const float*, float, void*, int);
+  const int vi = cv <= 64 ? 0 : cv <= 128 ? 1 : cv <= 192 ? 2 : 3;
+  static const LnsFn fn[4][2] = {{layernorm_split_kernel<1, false>, layernorm_split_kernel<1, true>},
+                                 {layernorm_split_kernel<2, false>, layernorm_split_kernel<2, true>},
+                                 {layernorm_split_kernel<3, false>, layernorm_split_kernel<3, true>},
+                                 {layernorm_split_kernel<5, false>, layernorm_split_kernel<5, true>}};
+  hipLaunchKernelGGL(fn[vi][out_f32 ? 1 : 0], grid, dim3(256), 0, s, x, ldx, x_lo, T, C, gamma, beta, eps, y, ldy);
+  return hipGetLastError();
+}
 
 hipError_t groupnorm_stats_grouped(const GnArgs* a, int n, int B, int HW, int C, int G, float eps,
                                    hipStream_t s) {

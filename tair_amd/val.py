@@ -147,6 +147,8 @@ def _parse(argv=None):
     ap.add_argument("--save-dir", default=None, help="overrides exp_args.save_val_img_dir")
     ap.add_argument("--ext", default=".jpg", help="image extensions, comma separated (the reference: .jpg)")
     ap.add_argument("--steps", type=int, default=50)
+    ap.add_argument("--clip-backend", default="torch", choices=["torch", "hip"],
+                    help="CLIP text tower: stock torch (default) or the HIP kernels (tair_amd/clip_hip.py)")
     return ap.parse_args(argv)
 
 
@@ -173,7 +175,8 @@ def main(argv=None) -> Dict[str, Optional[float]]:
     pairs = pair_images(gt_dir, lq_dir, [e.strip() for e in args.ext.split(",")])
     save_dir = args.save_dir or exp.get("save_val_img_dir") or "val_out"
 
-    model = build_model(cfg, max_batch=1, device=dev, with_clip=bool(args.weights)) if args.config else \
+    model = build_model(cfg, max_batch=1, device=dev, with_clip=bool(args.weights),
+                        clip_backend=args.clip_backend) if args.config else \
         ControlLDM(max_batch=1, device=dev)
     if args.weights:
         if args.weights.endswith(".safetensors"):

@@ -125,6 +125,8 @@ def _parse():
                          "reference passes it (val_patches.py:375; mis-grids multi-patch images)")
     ap.add_argument("--prompt", default="", help="text prompt for CLIP (needs TAIR_CLIP_BPE for non-empty prompts); "
                                                  "default: synthetic c_txt when no CLIP weights are given")
+    ap.add_argument("--clip-backend", default="torch", choices=["torch", "hip"],
+                    help="CLIP text tower: stock torch (default) or the HIP kernels (tair_amd/clip_hip.py)")
     return ap.parse_args()
 
 
@@ -149,7 +151,8 @@ def main():
     if args.config:
         from .config import build_diffusion, build_model, load_config
         cfg = load_config(args.config)
-        model = build_model(cfg, max_batch=args.tile_batch, device=dev, with_clip=bool(args.weights))
+        model = build_model(cfg, max_batch=args.tile_batch, device=dev, with_clip=bool(args.weights),
+                            clip_backend=args.clip_backend)
     else:
         model = ControlLDM(max_batch=args.tile_batch, device=dev)
     if args.weights:
