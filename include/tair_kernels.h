@@ -71,6 +71,11 @@ typedef struct {
    * W' = W diag(gamma), form v = rstd_m (acc - mean_m lncs[n]) + bias' with mean / rstd from lnst over
    * ln_c channels (eps ln_eps), lncs[n] = sum_k W'[n][k], bias' = bias + W beta. */
   double* rst; const double* lnst; const float* lncs; float ln_c; float ln_eps;
+  /* second GroupNorm statistics target (or st2_acc = NULL; needs st_acc): the same output also feeds a second
+   * GroupNorm, e.g. the decoder's norm over cat([h, skip]) in which this output's channels start at st2_coff.
+   * Its own accumulator, replica stride, group width and group count; it shares st_hw.  st_coff / st2_coff need
+   * not be multiples of the group width: a group may receive channels from two producers. */
+  double* st2_acc; int st2_rs, st2_cg, st2_G, st2_coff;
 } tair_gemm_desc;
 
 /* act: 0 none, 1 SiLU, 2 GEGLU — output channels packed as (x_2q, x_2q+1, gate_2q, gate_2q+1) groups,

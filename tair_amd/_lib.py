@@ -112,6 +112,8 @@ class GemmDesc(ctypes.Structure):
         ("stamps", ctypes.c_void_p),
         ("rst", ctypes.c_void_p), ("lnst", ctypes.c_void_p), ("lncs", ctypes.c_void_p), ("ln_c", ctypes.c_float),
         ("ln_eps", ctypes.c_float),
+        ("st2_acc", ctypes.c_void_p), ("st2_rs", ctypes.c_int), ("st2_cg", ctypes.c_int), ("st2_G", ctypes.c_int),
+        ("st2_coff", ctypes.c_int),
     ]
 
 

@@ -41,6 +41,10 @@ GemmArgs gemm_args_of(const tair_gemm_desc* d) {
     a.st[0].acc = d->st_acc; a.st[0].rs = d->st_rs; a.st[0].cg = d->st_cg; a.st[0].G = d->st_G;
     a.st[0].c_off = d->st_coff; a.st[0].hw = d->st_hw;
   }
+  if (d->st2_acc) {  // (without st_acc: refused by gemm_grouped)
+    a.st[1].acc = d->st2_acc; a.st[1].rs = d->st2_rs; a.st[1].cg = d->st2_cg; a.st[1].G = d->st2_G;
+    a.st[1].c_off = d->st2_coff; a.st[1].hw = d->st_hw;
+  }
   return a;
 }
 }  // namespace
