@@ -153,6 +153,31 @@ int tair_k_layernorm(const void* x, int T, int C, const float* gamma, const floa
  * sampler takes), row stride ldy elements.  C % 8 == 0, C <= 2560. */
 int tair_k_layernorm_split(const void* x, int ldx, int x_lo, int T, int C, const float* gamma, const float* beta,
                            float eps, void* y, int ldy, int out_f32, void* stream);
+/* The SwinIR cleaner's shifted-window attention (swinir.py:37-151 WindowAttention, :222-285 SwinTransformerBlock):
+ * softmax(q k^T * scale + relative-position bias + shift mask) v per 8x8 window and head of a [B, H, W] token map.
+ * Rows are pixels b * H * W + y * W + x, bf16; head h is at columns 32 h of q / k / v / o (operands may be strided
+ * out of one fused [T, 3 * 32 heads] buffer; leading dimensions % 8 == 0, 16-byte aligned pointers); d <= 32 is the
+ * real head dim: columns d..31 of a head are read as zero whatever they hold and written as zero in o.  The cyclic
+ * shift (torch.roll by -shift, :260-266) and window_partition (:37-51) are addressing: token (iy, ix) of window
+ * (wy, wx) is pixel ((8 wy + iy + shift) mod H, (8 wx + ix + shift) mod W), for the reads and for the write.  The mask
+ * (:222-243) comes from coordinates: y' = 8 wy + iy has region 0 if y' < H - 8, 1 if y' < H - shift, else 2, likewise
+ * x'; two tokens whose regions differ get the reference's finite -100; shift = 0: no mask.  bias_table fp32
+ * [225][heads] as the checkpoint stores it, entry (iy_q - iy_k + 7) * 15 + (ix_q - ix_k + 7) (:99-117).  Softmax in
+ * fp32 over the window's 64 keys in one pass, P rounded to bf16, both products on the bf16 MFMA.  H, W multiples of
+ * 8, 0 <= shift < 8.  Bad arguments: -1 with a message, before any launch. */
+int tair_k_window_attention(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo,
+                            int B, int H, int W, int heads, int d, int shift, const float* bias_table, float scale,
+                            void* stream);
+/* tair_k_layernorm_split for a channel count that is a multiple of 4 but not of 8 (SwinIR's 180: norm1 / norm2,
+ * patch_embed.norm, norm; swinir.py:245-285, :841-860), in rows padded to Cp columns: statistics over columns [0, C)
+ * of hi + lo (x_lo = 0: one plane), bf16 rows of stride ldy with zeros written to columns [C, Cp) (the next GEMM's
+ * K padding).  C % 4 == 0, C <= 1024, Cp >= C, Cp % 4 == 0.  Bad arguments: -1 with a message, before any launch. */
+int tair_k_layernorm_split_pad(const void* x, int ldx, int x_lo, int T, int C, int Cp, const float* gamma,
+                               const float* beta, float eps, void* y, int ldy, void* stream);
+/* LeakyReLU in place on bf16 rows (swinir.py:868-880: conv_before_upsample slope 0.01, conv_up* / conv_hr slope 0.2):
+ * x[r * ld + c] = x > 0 ? x : bf16(float(x) * slope) for c < C, bitwise F.leaky_relu on bf16.  C % 8 == 0, ld % 8 == 0,
+ * ld >= C.  Bad arguments: -1 with a message, before any launch. */
+int tair_k_leaky_relu(void* x, int ld, int rows, int C, float slope, void* stream);
 /* LayerNorm over C with e4m3 output for the fp8 linears (configs[4]): y8 [T][ld8] bytes (OCP e4m3,
  * bytes C..ld8 zeroed), s8 [T] per-token scale (max |y| / 448): y ~= y8 * s8. */
 int tair_k_layernorm_fp8(const void* x, int T, int C, const float* gamma, const float* beta, float eps, void* y8,

@@ -164,6 +164,9 @@ SIGNATURES = {
     "tair_k_attention_causal": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, ctypes.c_float, _P]),
     "tair_k_embed_tokens": (_I, [_P, _I, _I, _P, _I, _P, _I, _P, _I, _I, _P]),
     "tair_k_layernorm_split": (_I, [_P, _I, _I, _I, _I, _P, _P, ctypes.c_float, _P, _I, _I, _P]),
+    "tair_k_window_attention": (_I, [_P, _I, _P, _I, _P, _I, _P, _I, _I, _I, _I, _I, _I, _I, _P, ctypes.c_float, _P]),
+    "tair_k_layernorm_split_pad": (_I, [_P, _I, _I, _I, _I, _I, _P, _P, ctypes.c_float, _P, _I, _P]),
+    "tair_k_leaky_relu": (_I, [_P, _I, _I, _I, ctypes.c_float, _P]),
     "tair_k_groupnorm": (_I, [_P, _I, _I, _I, _I, _I, ctypes.c_float, _P, _P, _I, _P, _I, _P, _P, _P]),
     "tair_k_groupnorm_ex": (_I, [_P, _I, _I, _I, _I, _I, ctypes.c_float, _P, _P, _I, _P, _I, _P, _P, _P, _P]),
     "tair_k_layernorm": (_I, [_P, _I, _I, _P, _P, ctypes.c_float, _P, _P]),

@@ -81,13 +81,24 @@ SWINIR_VAL_PARAMS = dict(img_size=64, patch_size=1, in_chans=3, embed_dim=180, d
                          resi_connection="1conv", unshuffle=True, unshuffle_scale=8)
 
 
-def build_swinir(cfg: Optional[Dict[str, Any]], device, weights: Optional[str] = None):
-    """SwinIR(**cfg.model.swinir.params) (initialize.py: models['swinir']) on stock torch, eval mode;
-    reference-key weights from `weights`, else synthetic (seeded) weights."""
+def build_swinir(cfg: Optional[Dict[str, Any]], device, weights: Optional[str] = None, backend: str = "torch",
+                 max_batch: int = 4):
+    """SwinIR(**cfg.model.swinir.params) (initialize.py: models['swinir']), eval mode; reference-key weights
+    from `weights`, else synthetic (seeded) weights.  backend "torch" (the default): the stock module; "hip": the
+    same weights on the HIP kernels (swinir_hip.HipSwinIR: the val-config network only, workspaces for max_batch
+    512^2 images; needs a ROCm GPU); anything else is an error."""
+    if backend not in ("torch", "hip"):
+        raise ValueError(f"swinir backend must be 'torch' or 'hip', got {backend!r}")
     import torch
 
     from .swinir import SwinIR
     p = (_block(cfg, "swinir") if cfg is not None else None) or dict(SWINIR_VAL_PARAMS)
+    if backend == "hip":
+        from . import _lib, swinir_hip
+        swinir_hip.check_params(p)
+        dev = torch.device(device)
+        if dev.type != "cuda" or not torch.cuda.is_available():
+            raise _lib.TairError("swinir backend 'hip' needs a ROCm GPU (no CPU fallback)")
     m = SwinIR(**p)
     if weights:
         if weights.endswith(".safetensors"):
@@ -103,6 +114,8 @@ def build_swinir(cfg: Optional[Dict[str, Any]], device, weights: Optional[str] =
             for name, q in m.named_parameters():
                 if q.dim() > 1:
                     q.copy_(torch.randn(q.shape, generator=g) * (q[0].numel() ** -0.5))
+    if backend == "hip":
+        return swinir_hip.HipSwinIR(m.eval(), p, max_batch=max_batch, device=dev).eval()
     return m.to(device).eval()
 
 

@@ -142,6 +142,42 @@ int tair_k_layernorm_split(const void* x, int ldx, int x_lo, int T, int C, const
   return e == hipSuccess ? 0 : e == hipErrorInvalidValue ? -1 : -2;
 }
 
+int tair_k_window_attention(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo,
+                            int B, int H, int W, int heads, int d, int shift, const float* bias_table, float scale,
+                            void* stream) {
+  const hipError_t e = window_attention((const bf16*)q, ldq, (const bf16*)k, ldk, (const bf16*)v, ldv, (bf16*)o, ldo, B,
+                                        H, W, heads, d, shift, bias_table, scale, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) {
+    set_error("window_attention: bad arguments (B %d, token map %dx%d (multiples of 8), heads %d, d %d (1..32), shift %d "
+              "(0..7), scale %g, bias table %p, ld %d / %d / %d / %d: %% 8 and >= 32 heads, 16-byte aligned pointers)",
+              B, H, W, heads, d, shift, (double)scale, (const void*)bias_table, ldq, ldk, ldv, ldo);
+    return -1;
+  }
+  return e == hipSuccess ? 0 : -2;
+}
+
+int tair_k_layernorm_split_pad(const void* x, int ldx, int x_lo, int T, int C, int Cp, const float* gamma,
+                               const float* beta, float eps, void* y, int ldy, void* stream) {
+  const hipError_t e = layernorm_split_pad((const bf16*)x, ldx, x_lo, T, C, Cp, gamma, beta, eps, (bf16*)y, ldy,
+                                           (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) {
+    set_error("layernorm_split_pad: bad arguments (T %d, C %d (%% 4, <= 1024), Cp %d (>= C, %% 4), ldx %d, x_lo %d, "
+              "ldy %d (>= Cp); ld %% 4, 8-byte aligned rows, 16-byte aligned gamma / beta)", T, C, Cp, ldx, x_lo, ldy);
+    return -1;
+  }
+  return e == hipSuccess ? 0 : -2;
+}
+
+int tair_k_leaky_relu(void* x, int ld, int rows, int C, float slope, void* stream) {
+  const hipError_t e = leaky_relu((bf16*)x, ld, rows, C, slope, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) {
+    set_error("leaky_relu: bad arguments (rows %d, C %d, ld %d: C, ld %% 8, ld >= C, 16-byte aligned pointer)", rows, C,
+              ld);
+    return -1;
+  }
+  return e == hipSuccess ? 0 : -2;
+}
+
 int tair_k_groupnorm(const void* x, int ldx, int B, int HW, int C, int G, float eps, const float* gamma,
                      const float* beta, int silu, void* y, int ldy, float* ss, float* ws, void* stream) {
   hipStream_t s = (hipStream_t)stream;

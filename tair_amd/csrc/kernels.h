@@ -325,6 +325,20 @@ hipError_t layernorm_split(const bf16* x, int ldx, int x_lo, int T, int C, const
                            float eps, void* y, int ldy, int out_f32, hipStream_t s);
 int* gemm_fault_word();  // the current device's fault counter (null before gemm_init)
 
+// ---- SwinIR cleaner (swinir.hip; swinir.py:37-151, :245-285, :841-894) --------------------------
+// O = softmax(Q K^T * scale + relative-position bias + shift mask) V per 8x8 window and head of a [B, H, W] token map
+// (rows b * H * W + y * W + x of q / k / v / o, head h at columns 32 h, real head dim d <= 32: columns d..31 read
+// as zero and written as zero).  shift > 0: the windows of the map rolled by (-shift, -shift), as addressing;
+// bias_table fp32 [225][heads].  hipErrorInvalidValue for a bad shape, before any launch
+hipError_t window_attention(const bf16* q, int ldq, const bf16* k, int ldk, const bf16* v, int ldv, bf16* o, int ldo,
+                            int B, int H, int W, int heads, int d, int shift, const float* bias_table, float scale,
+                            hipStream_t s);
+// layernorm_split for C % 4 == 0 in rows padded to Cp columns: statistics over [0, C), bf16 out, zeros at [C, Cp)
+hipError_t layernorm_split_pad(const bf16* x, int ldx, int x_lo, int T, int C, int Cp, const float* gamma,
+                               const float* beta, float eps, bf16* y, int ldy, hipStream_t s);
+// in place on bf16 rows: x = x > 0 ? x : bf16(float(x) * slope); C, ld % 8 == 0
+hipError_t leaky_relu(bf16* x, int ld, int rows, int C, float slope, hipStream_t s);
+
 // ---- misc ---------------------------------------------------------------------------------
 hipError_t geglu(const bf16* xg, int T, int D, bf16* y, hipStream_t s);
 hipError_t timestep_sinusoid(const int64_t* t, int n, int dim, float* out, hipStream_t s);

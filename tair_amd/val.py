@@ -141,6 +141,8 @@ def _parse(argv=None):
     ap.add_argument("--weights", default=None, help="state dict (.pt/.safetensors) with reference keys (default: synthetic)")
     ap.add_argument("--testr-weights", default=None)
     ap.add_argument("--swinir-weights", default=None)
+    ap.add_argument("--swinir-backend", choices=("torch", "hip"), default="torch",
+                    help="SwinIR cleaner on stock torch (default) or on the HIP kernels (tair_amd/swinir_hip.py)")
     ap.add_argument("--no-swinir", action="store_true", help="skip the SwinIR cleaner (the reference always runs it)")
     ap.add_argument("--gt-dir", default=None, help="overrides dataset.gt_img_path")
     ap.add_argument("--lq-dir", default=None, help="overrides dataset.lq_img_path")
@@ -191,7 +193,8 @@ def main(argv=None) -> Dict[str, Optional[float]]:
     diffusion = build_diffusion(cfg) if args.config else Diffusion(linear_start=0.00085, linear_end=0.012,
                                                                    zero_snr=True, parameterization="v")
     sampler = SpacedSampler(diffusion.betas, diffusion.parameterization, False)
-    cleaner = None if args.no_swinir else build_swinir(cfg or None, dev, args.swinir_weights)
+    cleaner = None if args.no_swinir else build_swinir(cfg or None, dev, args.swinir_weights,
+                                                             backend=args.swinir_backend)
     ts_model, style = None, exp.get("prompt_style") or "CAPTION"
     c_txt = None
     if args.config_testr:

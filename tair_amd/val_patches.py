@@ -120,6 +120,8 @@ def _parse():
                     "params from --config model.swinir (else the val config's), weights from --swinir-weights "
                     "(else synthetic)")
     ap.add_argument("--swinir-weights", default=None, help="SwinIR state dict (.pth / .safetensors, reference keys)")
+    ap.add_argument("--swinir-backend", choices=("torch", "hip"), default="torch",
+                    help="SwinIR cleaner on stock torch (default) or on the HIP kernels (tair_amd/swinir_hip.py)")
     ap.add_argument("--merge-size", default="lq", choices=["lq", "gt"],
                     help="original_size of the overlap merge: the LQ size (correct grid) or the GT size as the "
                          "reference passes it (val_patches.py:375; mis-grids multi-patch images)")
@@ -178,7 +180,7 @@ def main():
     cleaner = None
     if args.swinir:
         from .config import build_swinir
-        cleaner = build_swinir(cfg, dev, args.swinir_weights)
+        cleaner = build_swinir(cfg, dev, args.swinir_weights, backend=args.swinir_backend)
     ts_model, style = None, args.prompt_style
     if args.config_testr:
         from .config import build_testr
