@@ -108,6 +108,10 @@ int tair_k_kgroup_tile(int kt0, int g, int trip);
 /* The plan tair_k_attention would launch (host only, no device needed): queries per wave / 16 (qsets),
  * key splits and keys per split, for a workspace of ws_bytes (< 0: unbounded). 0 on success. */
 int tair_k_attention_plan(int B, int H, int Sq, int Skv, int64_t ws_bytes, int* qsets, int* splits, int* kv_split);
+/* Same for the forced forms (force_qsets / force_splits of tair_k_attention_ex / _tk, 0 = heuristic): the plan
+ * that call launches, after the clamps to the key-tile count and to the workspace. */
+int tair_k_attention_plan_ex(int B, int H, int Sq, int Skv, int64_t ws_bytes, int force_qsets, int force_splits,
+                             int* qsets, int* splits, int* kv_split);
 /* softmax(Q K^T * scale) V, head dim 64 (attention.py:168-216). */
 int tair_k_attention(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo,
                      int B, int H, int Sq, int Skv, int kv_bstride, float scale, void* stream);

@@ -88,6 +88,19 @@ int tair_k_attention_plan(int B, int H, int Sq, int Skv, int64_t ws_bytes, int* 
   return 0;
 }
 
+int tair_k_attention_plan_ex(int B, int H, int Sq, int Skv, int64_t ws_bytes, int force_qsets, int force_splits,
+                             int* qsets, int* splits, int* kv_split) {
+  if (!qsets || !splits || !kv_split || B < 1 || H < 1 || Sq < 1 || Skv < 1 || force_qsets < 0 || force_qsets > 2 ||
+      force_splits < 0)
+    return -1;
+  const AttnPlan p = attention_plan(B, H, Sq, Skv, ws_bytes < 0 ? (size_t)-1 : (size_t)ws_bytes, force_qsets,
+                                    force_splits);
+  *qsets = p.qsets;
+  *splits = p.splits;
+  *kv_split = p.kv_split;
+  return 0;
+}
+
 int tair_k_attention(const void* q, int ldq, const void* k, int ldk, const void* v, int ldv, void* o, int ldo,
                      int B, int H, int Sq, int Skv, int kv_bstride, float scale, void* stream) {
   return attention((const bf16*)q, ldq, (const bf16*)k, ldk, (const bf16*)v, ldv, (bf16*)o, ldo, B, H, Sq, Skv,
