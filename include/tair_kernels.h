@@ -262,6 +262,36 @@ int tair_k_tile_blend_step(float* x, const float* v, float* v_blend, float* acc,
                            const float* noise, int B, int H, int W, int tile, int stride, int rows_per_chunk,
                            int n_chunks, int C, void* stream);
 
+/* Tiling of the SwinIR cleaner over an image larger than one tile (utils/common.py:174-234 make_tiled_fn as
+ * pipeline.py:371-397 wraps the cleaner: scale 1, Gaussian weights, fp32 accumulators, no padding), the two kernels
+ * HipSwinIR.forward_tiled launches around every chunk of window rows.  Geometry: B images [3, H, W], tile x tile
+ * windows (tile a multiple of 64, <= H and W) at `stride` (starts 0, stride, ... plus one flush with the edge when
+ * the stride does not divide, so a window may start at any pixel; row-major; T per image), job rows j = b * T + k.
+ * A call handles the `rows` chunk rows that start at job row `first` (0 <= first < B * T, rows >= 1); a chunk row
+ * past the job's last row is a pad row.  Both calls are capturable and never synchronise; a bad argument (tile not
+ * a multiple of 64 or larger than the image, stride < 1, first / rows out of range, a null pointer, ld too small)
+ * is -1 with a message, before any launch.
+ *
+ * tair_k_image_tile_gather: x [B, 3, H, W] fp32 NCHW, mean [3] fp32.  Chunk row r gets its window as the network's
+ * input: token (ty, tx) of the tile/8 x tile/8 token map is row r * (tile/8)^2 + ty * (tile/8) + tx of `in` (bf16,
+ * ld elements a row), column c * 64 + dy * 8 + dx holds pixel (8 ty + dy, 8 tx + dx) of channel c of the window as
+ * two planes, hi = bf16(u) at the column and lo = bf16(u - float(hi)) lo_off columns further on, u = fl(x - mean[c]):
+ * bitwise the torch expression pixel_unshuffle(x - mean, 8) split hi | lo.  lo_off >= 192, lo_off + 192 <= ld, both
+ * even, `in` 4-byte aligned.  A pad row gets the job's last window; other columns of a row are left alone. */
+int tair_k_image_tile_gather(const float* x, const float* mean, int B, int H, int W, int tile, int stride, int first,
+                             int rows, void* in, int ld, int lo_off, void* stream);
+/* tair_k_image_tile_blend: v [rows * tile^2, 3] fp32 NHWC is the network's output for the chunk (conv_last's rows as
+ * they stand), weights [tile^2] fp32.  One thread per image element (b, c, y, x) adds, over the chunk's job rows
+ * whose window covers the pixel, in ascending window order,
+ *   acc = fl(acc + fl(v * w)),  cnt = fl(cnt + w)     (the product is rounded before it is added)
+ * into acc, cnt [B, 3, H, W] fp32; with first == 0 both start from zero inside the kernel (no memset).  Chunks
+ * ascend and windows ascend inside a chunk, so the sums are the reference loop's and do not depend on the chunking;
+ * pad rows are never read.  finalize != 0 (only on the chunk that ends the job): out [B, 3, H, W] = acc / cnt, an
+ * IEEE-rounded division, instead of storing the accumulators.  A pixel under a single window is fl(fl(v w) / w),
+ * as in the reference (unlike tair_k_tile_blend_step). */
+int tair_k_image_tile_blend(const float* v, const float* weights, float* acc, float* cnt, float* out, int B, int H,
+                            int W, int tile, int stride, int first, int rows, int finalize, void* stream);
+
 /* Overlap-blend stitch of decoded tiles on the device (val_patches.py:114-206 merge_patches_with_overlap,
  * stride generalised): tiles [n_tiles][C][patch][patch] fp32 on a raster nh x nw grid, out [C][H][W]
  * fp32 cropped; rtab[i] = fp32((i+1)/overlap), i < overlap (device).  Bitwise the reference loop. */

@@ -182,6 +182,8 @@ SIGNATURES = {
     "tair_k_tile_gather": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _P, _I, _I, _I, _P]),
     "tair_k_tile_blend_step": (_I, [_P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I,
                                     _P]),
+    "tair_k_image_tile_gather": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _P]),
+    "tair_k_image_tile_blend": (_I, [_P, _P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _P]),
     "tair_k_merge_overlap": (_I, [_P, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P]),
     "tair_k_stitch_peers": (_I, [_P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _I, _P, _I, _I, _I, _P, _P]),
     "tair_ipc_get_handle": (_I, [_P, _P, ctypes.POINTER(ctypes.c_ulonglong)]),

@@ -286,6 +286,33 @@ int tair_k_tile_blend_step(float* x, const float* v, float* v_blend, float* acc,
   return e == hipSuccess ? 0 : -2;
 }
 
+int tair_k_image_tile_gather(const float* x, const float* mean, int B, int H, int W, int tile, int stride, int first,
+                             int rows, void* in, int ld, int lo_off, void* stream) {
+  const hipError_t e = image_tile_gather(x, mean, ImageTileGeom{B, H, W, tile, stride, first, rows}, (bf16*)in, ld,
+                                         lo_off, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) {
+    set_error("image_tile_gather: bad arguments (B %d, image %dx%d, tile %d (%% 64, <= H, W), stride %d, first %d, "
+              "rows %d, ld %d, lo_off %d (>= 192, even, lo_off + 192 <= ld), null x %d, mean %d, in %d)", B, H, W, tile,
+              stride, first, rows, ld, lo_off, x == nullptr, mean == nullptr, in == nullptr);
+    return -1;
+  }
+  return e == hipSuccess ? 0 : -2;
+}
+
+int tair_k_image_tile_blend(const float* v, const float* weights, float* acc, float* cnt, float* out, int B, int H,
+                            int W, int tile, int stride, int first, int rows, int finalize, void* stream) {
+  const hipError_t e = image_tile_blend(v, weights, acc, cnt, out, finalize,
+                                        ImageTileGeom{B, H, W, tile, stride, first, rows}, (hipStream_t)stream);
+  if (e == hipErrorInvalidValue) {
+    set_error("image_tile_blend: bad arguments (B %d, image %dx%d, tile %d (%% 64, <= H, W), stride %d, first %d, "
+              "rows %d, finalize %d (only on the chunk that ends the job, with out), null v %d, weights %d, acc %d, "
+              "cnt %d, out %d)", B, H, W, tile, stride, first, rows, finalize, v == nullptr, weights == nullptr,
+              acc == nullptr, cnt == nullptr, out == nullptr);
+    return -1;
+  }
+  return e == hipSuccess ? 0 : -2;
+}
+
 int tair_k_merge_overlap(const float* tiles, int n_tiles, int nh, int nw, int patch, int overlap, int stride,
                          float* out, int C, int H, int W, const float* rtab, void* stream) {
   return merge_overlap(tiles, n_tiles, nh, nw, patch, overlap, stride, out, C, H, W, rtab, (hipStream_t)stream) ==

@@ -416,6 +416,21 @@ struct TileBlendArgs {
 };
 hipError_t tile_blend_step(const TileBlendArgs& a, hipStream_t s);
 
+// ---- tiled SwinIR cleaner (image_tile.hip; utils/common.py:174-234 as pipeline.py:371-397 uses it) ----
+// B images [3, H, W] in S x S windows (S % 64 == 0) at `stride`, windowed as above; one call handles the `rows`
+// chunk rows that start at job row `first` (rows past the job's end are pad).
+struct ImageTileGeom {
+  int B, H, W, S, stride, first, rows;
+};
+// x [B, 3, H, W] fp32 -> chunk row r's window, mean-subtracted and pixel-unshuffled by 8, as the planes
+// hi = bf16(u) at in[(r * (S/8)^2 + token) * ld + col] and lo = bf16(u - hi) lo_off columns further on
+hipError_t image_tile_gather(const float* x, const float* mean, const ImageTileGeom& t, bf16* in, int ld, int lo_off,
+                             hipStream_t s);
+// v [rows * S * S, 3] fp32 NHWC, w [S * S]: acc += fl(v w), cnt += w over the chunk's job rows in ascending order
+// (from zero when first == 0); finalize: out [B, 3, H, W] = acc / cnt instead of storing the accumulators
+hipError_t image_tile_blend(const float* v, const float* w, float* acc, float* cnt, float* out, int finalize,
+                            const ImageTileGeom& t, hipStream_t s);
+
 // Multi-scale deformable attention sampling (TESTR, msda.hip): level shapes by value (capturable)
 constexpr int MSDA_MAX_LEVELS = 8;
 struct MsdaArgs {

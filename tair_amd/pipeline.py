@@ -70,8 +70,9 @@ class Restorer:
 # terediff/pipeline.py call surface (SURVEY §2 "call surface only", VERDICT r3 missing 5): Pipeline.run /
 # apply_cldm and SwinIRPipeline.apply_cleaner as thin callers of the HIP ControlLDM and SpacedSampler.
 # The tiled VAE (vae_encoder_tiled / vae_decoder_tiled, utils/tilevae/tilevae.py with fast mode off) runs on a
-# handle that has it (ControlLDM.vae_tiling).  The reference's other samplers (DDIM / DPM / EDM), restoration
-# guidance (cond_fn) and tiled SwinIR are out of scope and raise NotImplementedError when asked for.
+# handle that has it (ControlLDM.vae_tiling), the tiled cleaner on a cleaner that declares it (`tiling`: HipSwinIR,
+# the stock SwinIR).  The reference's other samplers (DDIM / DPM / EDM) and restoration guidance (cond_fn) are out
+# of scope and raise NotImplementedError when asked for.
 # ---------------------------------------------------------------------------------------------------
 def resize_short_edge_to(imgs: torch.Tensor, size: int) -> torch.Tensor:
     """pipeline.py:25-34."""
@@ -130,7 +131,7 @@ class Pipeline:
     path) -> HIP VAE decode -> wavelet colour fix -> bicubic resize -> uint8.
 
     Differences from the reference, all explicit: `sampler_type` must be "spaced" (the others are out of
-    scope); `cond_fn` must be None; the tiled SwinIR option must be False; the HIP ControlLDM has a
+    scope); `cond_fn` must be None; the tiled SwinIR option needs a cleaner that declares `tiling`; the HIP ControlLDM has a
     fixed latent size (its workspace is sized at creation), so the padded condition image must be
     8 x latent_hw, or, with `cldm_tiled` (latent tiling inside the sampling loop, pipeline.py:97-144, 203-218),
     any size of at least `cldm_tile_size` = 8 x latent_hw per side; there `vae_encoder_tiled` /
@@ -291,11 +292,27 @@ class Pipeline:
 
 
 class SwinIRPipeline(Pipeline):
-    """pipeline.py:369-397 (untiled: short edge to 512, pad to 64, SwinIR, crop)."""
+    """pipeline.py:369-397.  Untiled: short edge to 512, pad to 64, SwinIR, crop.  Tiled (a cleaner that declares
+    ``tiling``: HipSwinIR through its forward_tiled, the stock SwinIR through tiling.make_tiled_fn): no padding,
+    overlapping tile_size windows blended with Gaussian weights, the short edge resized to 512 after cleaning."""
 
     def apply_cleaner(self, lq: torch.Tensor, tiled: bool, tile_size: int, tile_stride: int) -> torch.Tensor:
+        if tiled and not getattr(self.cleaner, "tiling", False):  # a cleaner without it keeps refusing it
+            raise NotImplementedError("tiled SwinIR is served by a cleaner that declares `tiling` (HipSwinIR, "
+                                      "tair_amd.swinir.SwinIR) only")
+        if tiled and (lq.size(2) < tile_size or lq.size(3) < tile_size):
+            tiled = False  # :374-376 "the input size is tiny and unnecessary to tile"
         if tiled:
-            raise NotImplementedError("tiled SwinIR is out of scope (SURVEY §2)")
+            if tile_size % 64 != 0:  # :378-379
+                raise ValueError("SwinIR (cleaner) tile size must be a multiple of 64")
+            if hasattr(self.cleaner, "forward_tiled"):
+                output = self.cleaner.forward_tiled(lq, tile_size, tile_stride)
+            else:
+                from .tiling import make_tiled_fn
+                output = make_tiled_fn(self.cleaner, size=tile_size, stride=tile_stride)(lq)
+            if min(output.shape[2:]) < 512:  # :395-396: in tiled mode the resize follows the cleaner
+                output = resize_short_edge_to(output, size=512)
+            return output
         if min(lq.shape[2:]) < 512:
             lq = resize_short_edge_to(lq, size=512)
         h0, w0 = lq.shape[2:]

@@ -154,6 +154,8 @@ class SwinIR(nn.Module):
     """Constructor arguments as terediff/model/swinir.py:652-681 (training-only ones accepted and
     ignored); `upsampler` '' (residual restoration), 'nearest+conv' or 'pixelshuffle'."""
 
+    tiling = True  # SwinIRPipeline.apply_cleaner(tiled=True) is served, by tiling.make_tiled_fn over this module
+
     def __init__(self, img_size=64, patch_size=1, in_chans=3, embed_dim=96, depths: Sequence[int] = (6, 6, 6, 6),
                  num_heads: Sequence[int] = (6, 6, 6, 6), window_size=7, mlp_ratio=4.0, qkv_bias=True, sf=4,
                  img_range=1.0, upsampler="", resi_connection="1conv", unshuffle=False, unshuffle_scale=None,

@@ -23,7 +23,11 @@ Driven from Python over the kernel ABI (include/tair_kernels.h), as clip_hip.py 
   2 + 7 blocks + groups + 3 + 10 launches.
 
 The boundary conversions (mean, pixel-unshuffle, NCHW <-> NHWC, the hi / lo split of the input) are device torch
-ops.  Workspaces are sized at construction for ``max_batch`` images of a ``max_hw`` token map; a forward launches
+ops in ``forward``.  ``forward_tiled`` (an image larger than the workspaces: utils/common.py:174-234 as
+pipeline.py:389-394 wraps the cleaner) runs the same launch list on chunks of overlapping windows between two
+kernels of csrc/image_tile.hip: tair_k_image_tile_gather writes the windows as the two-plane input (the boundary
+conversions inside it), tair_k_image_tile_blend adds conv_last's fp32 rows into whole-image accumulators with the
+Gaussian weights in the reference loop's order and divides on the last chunk.  Workspaces are sized at construction for ``max_batch`` images of a ``max_hw`` token map; a forward launches
 on the current stream only, never synchronises and is capturable.  A missing kernel or a refused plan raises
 ``TairError``: there is no fallback to torch.
 """
@@ -252,10 +256,33 @@ def check_input(shape, max_hw: Tuple[int, int]) -> Tuple[int, int, int]:
     return int(shape[0]), h, w
 
 
+def check_tiled_input(shape, tile_size: int, tile_stride: int, max_hw: Tuple[int, int]) -> Tuple[int, int, int, int]:
+    """(B, H, W, t) of a tiled call, t the side of a window's token map; ValueError unless the input is [B, 3, H, W]
+    with H, W >= tile_size, tile_size a multiple of 64 whose token map fits max_hw, and tile_stride >= 1."""
+    if len(shape) != 4 or shape[0] < 1 or shape[1] != 3:
+        raise ValueError(f"HipSwinIR: input {tuple(shape)} (need [B, 3, H, W])")
+    tile_size, tile_stride = int(tile_size), int(tile_stride)
+    if tile_size < SF * WS or tile_size % (SF * WS):
+        raise ValueError(f"HipSwinIR: tile size {tile_size} must be a multiple of {SF * WS}")
+    if tile_stride < 1:
+        raise ValueError(f"HipSwinIR: tile stride {tile_stride} must be >= 1")
+    t = tile_size // SF
+    if t * t > max_hw[0] * max_hw[1]:
+        raise ValueError(f"HipSwinIR: a {tile_size} tile's token map {t}x{t} exceeds the {max_hw[0]}x{max_hw[1]} the "
+                         "workspaces were built for")
+    H, W = int(shape[2]), int(shape[3])
+    if H < tile_size or W < tile_size:
+        raise ValueError(f"HipSwinIR: image {H}x{W} is smaller than the tile {tile_size}")
+    return int(shape[0]), H, W, t
+
+
 class HipSwinIR(nn.Module):
     """SwinIR (val config) on the HIP kernels: ``forward(x)`` as the stock module, x [B, 3, H, W] fp32 in [0, 1]
-    with H, W multiples of 64 -> [B, 3, H, W] fp32.  ``src``: a tair_amd.swinir.SwinIR or a reference-key state
-    dict; ``params``: its constructor arguments (checked: the val-config network only)."""
+    with H, W multiples of 64 -> [B, 3, H, W] fp32; ``forward_tiled(x, tile_size, tile_stride)`` for an image
+    larger than the workspaces.  ``src``: a tair_amd.swinir.SwinIR or a reference-key state dict; ``params``: its
+    constructor arguments (checked: the val-config network only)."""
+
+    tiling = True  # SwinIRPipeline.apply_cleaner(tiled=True) is served, by forward_tiled
 
     def __init__(self, src, params: dict, *, max_batch: int = 4, max_hw: Tuple[int, int] = (64, 64), device="cuda"):
         super().__init__()
@@ -275,6 +302,9 @@ class HipSwinIR(nn.Module):
         self._L = _lib.lib()
         self._plans: Dict[tuple, List] = {}
         self._keep: List = []
+        self._tiled: Dict[tuple, Tuple[torch.Tensor, torch.Tensor]] = {}  # (B, H, W, tile, stride) -> acc, cnt
+        self._weights: Dict[int, torch.Tensor] = {}                      # tile -> fp32 Gaussian weights [tile, tile]
+        self.last_tiling: Optional[Dict] = None                          # the plan of the last forward_tiled
         self._depths = [int(d) for d in packed["depths"]]
         for name, t in packed.items():
             self.register_buffer(name, t.to(dev).contiguous())
@@ -419,6 +449,50 @@ class HipSwinIR(nn.Module):
             for fn, args, name in ops:
                 _lib.check(fn(*args, stream), f"SwinIR {name}")
         return self._o32[:64 * T].view(B, SF * h, SF * w, 3).permute(0, 3, 1, 2).contiguous()
+
+    @torch.no_grad()
+    def forward_tiled(self, x: torch.Tensor, tile_size: int, tile_stride: int) -> torch.Tensor:
+        """The cleaner over an image larger than the workspaces (utils/common.py:174-234 make_tiled_fn as
+        pipeline.py:389-394 wraps the cleaner): x [B, 3, H, W] fp32 with H, W >= tile_size (any size: no padding, a
+        window may start at any pixel), tile_size a multiple of 64 whose token map fits max_hw -> [B, 3, H, W] fp32.
+        The B x T window rows run in equal chunks of at most max_batch (tiling.plan_image_tiles); per chunk
+        tair_k_image_tile_gather writes the windows as the network's input, the launch list of forward runs on them
+        unchanged, and tair_k_image_tile_blend adds conv_last's output into whole-image fp32 accumulators in the
+        reference loop's order, dividing by the accumulated weight on the last chunk.  The accumulators and weights
+        are kept per (B, H, W, tile, stride) and the first chunk starts them from zero, so the call holds no state:
+        it launches on the current stream only, never synchronises and is capturable as a whole.  ``last_tiling``
+        holds the plan of the last call."""
+        from .tiling import gaussian_weights, plan_image_tiles
+        B, H, W, t = check_tiled_input(x.shape, tile_size, tile_stride, self.max_hw)
+        tile_size, tile_stride = int(tile_size), int(tile_stride)
+        plan = plan_image_tiles(B, H, W, tile_size, tile_stride, self.max_batch)
+        dev = self.mean.device
+        rpc = plan["rows_per_chunk"]
+        ops = self._plan(rpc, t, t)
+        x = x.to(device=dev, dtype=torch.float32).contiguous()
+        if tile_size not in self._weights:
+            self._weights[tile_size] = torch.tensor(gaussian_weights(tile_size, tile_size), dtype=torch.float32).to(dev)
+        key = (B, H, W, tile_size, tile_stride)
+        if key not in self._tiled:
+            self._tiled[key] = (torch.empty((B, 3, H, W), dtype=torch.float32, device=dev),
+                                torch.empty((B, 3, H, W), dtype=torch.float32, device=dev))
+        acc, cnt = self._tiled[key]
+        wts = self._weights[tile_size]
+        out = torch.empty((B, 3, H, W), dtype=torch.float32, device=dev)
+        p = lambda a: ctypes.c_void_p(a.data_ptr())  # noqa: E731
+        lib = self._L
+        with torch.cuda.device(dev):
+            stream = ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream)
+            for c, (first, _) in enumerate(plan["chunks"]):
+                _lib.check(lib.tair_k_image_tile_gather(p(x), p(self.mean), B, H, W, tile_size, tile_stride, first, rpc,
+                                                        p(self._in), 2 * CP, CP, stream), "SwinIR image_tile_gather")
+                for fn, args, name in ops:
+                    _lib.check(fn(*args, stream), f"SwinIR {name}")
+                _lib.check(lib.tair_k_image_tile_blend(p(self._o32), p(wts), p(acc), p(cnt), p(out), B, H, W, tile_size,
+                                                       tile_stride, first, rpc, int(c == plan["n_chunks"] - 1), stream),
+                           "SwinIR image_tile_blend")
+        self.last_tiling = plan
+        return out
 
     def check_faults(self):
         """Raise when a kernel reported a fault since the last check (a cooperative split-K wait that timed

@@ -167,3 +167,41 @@ def plan_latent_tiles(B: int, H: int, W: int, size: int, stride: int, max_batch:
     rows_per_chunk = -(-n // n_chunks)
     return dict(windows=windows, rows=n, cap=cap, n_chunks=n_chunks, rows_per_chunk=rows_per_chunk,
                 pad=n_chunks * rows_per_chunk - n)
+
+
+# ---------------------------------------------------------------------------------------------------
+# tiled cleaner (utils/common.py:174-234 make_tiled_fn as pipeline.py:371-397 wraps the cleaner in it)
+# ---------------------------------------------------------------------------------------------------
+def plan_image_tiles(B: int, H: int, W: int, size: int, stride: int, max_batch: int) -> Dict:
+    """The rows one tiled cleaner call runs: plan_latent_tiles without guidance on an image of H x W pixels, plus
+    `chunks`, the (first job row, job rows) of every forward (the last one is `pad` rows short of rows_per_chunk)."""
+    if size < 1 or size % 64 != 0:
+        raise ValueError(f"SwinIR (cleaner) tile size {size} must be a multiple of 64")
+    if H < size or W < size:
+        raise ValueError(f"image {H}x{W} is smaller than the tile {size}")
+    plan = plan_latent_tiles(B, H, W, size, stride, max_batch, guided=False)
+    rpc, n = plan["rows_per_chunk"], plan["rows"]
+    plan["chunks"] = [(c * rpc, min(rpc, n - c * rpc)) for c in range(plan["n_chunks"])]
+    return plan
+
+
+def make_tiled_fn(fn, size: int, stride: int):
+    """utils/common.py:174-234 in the form pipeline.py:389-394 uses (scale 1, Gaussian weights): fn runs on every
+    size x size window of x [B, C, H, W] (all images of the batch at once, windows in sliding_windows order), each
+    output is multiplied by the fp32 Gaussian weights and added into an fp32 accumulator, the weights into a second
+    one, and the result is their quotient.  Stock torch, on x's device; for cleaners that are ordinary modules."""
+    if stride < 1:
+        raise ValueError(f"tile stride {stride} must be >= 1")
+
+    def tiled_fn(x: torch.Tensor) -> torch.Tensor:
+        b, c, h, w = x.shape
+        if h < size or w < size:
+            raise ValueError(f"image {h}x{w} is smaller than the tile {size}")
+        out = torch.zeros((b, c, h, w), dtype=torch.float32, device=x.device)
+        count = torch.zeros_like(out)
+        weights = torch.tensor(gaussian_weights(size, size)[None, None], dtype=torch.float32, device=x.device)
+        for y0, y1, x0, x1 in sliding_windows(h, w, size, stride):
+            out[..., y0:y1, x0:x1] += fn(x[..., y0:y1, x0:x1]) * weights
+            count[..., y0:y1, x0:x1] += weights
+        return out / count
+    return tiled_fn
