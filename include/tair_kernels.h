@@ -98,6 +98,42 @@ int tair_k_gemm_desc_bytes(void);
  * 5 two-K-group 64-row tile).
  * Returns the validation status tair_k_gemm would report. */
 int tair_k_gemm_plan(const tair_gemm_desc* d, int* bm, int* bn, int* splits, int* kern);
+/* Grouped launches (tests of the two-lane path): d is an array of n (1 or 2) descriptors of one shape, mode and
+ * epilogue kind, run as lanes 0 .. n - 1 of ONE launch (a UNet layer and the same ControlNet layer in the product).
+ * The plan is lane 0's request (force_*, probe) for n lanes; every lane brings its own operands, outputs, split-K
+ * workspace and tickets.  out_f32 and out_split are shared; out_lo, the time embedding, the residual and the
+ * statistics targets may differ.  Any other n: refused, nothing launched. */
+int tair_k_gemm_grouped(const tair_gemm_desc* d, int n, void* stream);
+/* tair_k_gemm_plan for `lanes` (1 or 2) lanes of d. */
+int tair_k_gemm_plan_lanes(const tair_gemm_desc* d, int lanes, int* bm, int* bn, int* splits, int* kern);
+/* The validation and planning of tair_k_gemm_grouped for the n descriptors at d, without launching (host only, no
+ * device needed): 0, or -2 with tair_last_error. */
+int tair_k_gemm_grouped_check(const tair_gemm_desc* d, int n);
+/* tair_k_attention_tk for n (1 or 2) lanes of one shape in one launch: each lane its own q / k / v / o, key-split
+ * workspace (or NULL) and tickets (or NULL). */
+typedef struct {
+  const void* q; int ldq; const void* k; int ldk; const void* v; int ldv; void* o; int ldo; int kv_bstride;
+  void* ws; int64_t ws_bytes; int* tickets; int tickets_cap;
+} tair_attn_lane;
+int tair_k_attention_grouped(const tair_attn_lane* lanes, int n, int B, int H, int Sq, int Skv, float scale,
+                             int force_qsets, int force_splits, void* stream);
+/* tair_k_layernorm (y) / tair_k_layernorm_fp8 (y8, s8, ld8; y may be NULL) for n (1 or 2) lanes in one launch. */
+typedef struct {
+  const void* x; const float* gamma; const float* beta; void* y; void* y8; float* s8; int ld8;
+} tair_ln_lane;
+int tair_k_layernorm_grouped(const tair_ln_lane* lanes, int n, int T, int C, float eps, void* stream);
+/* GroupNorm for n (1 or 2) lanes per launch.  tair_k_groupnorm_grouped: statistics (tickets in every lane: one
+ * launch; else two) into ss, then the apply from ss, as tair_k_groupnorm_ex.  tair_k_gn_apply_stats_grouped: the
+ * apply from producer statistics st (every lane), as tair_k_gn_apply_stats (y, y_split) or tair_k_gn_apply_fp8 (y8,
+ * ld8, inv8), with x_lo. */
+typedef struct {
+  const void* x; int ldx; const float* gamma; const float* beta; float* ss; float* ws; int* tickets;
+  void* y; int ldy; const double* st; int st_rs; int x_lo; int y_split; void* y8; int ld8; const float* inv8;
+} tair_gn_lane;
+int tair_k_groupnorm_grouped(const tair_gn_lane* lanes, int n, int B, int HW, int C, int G, float eps, int silu,
+                             void* stream);
+int tair_k_gn_apply_stats_grouped(const tair_gn_lane* lanes, int n, int B, int HW, int C, int G, float eps, int silu,
+                                  void* stream);
 /* The two-K-group 64-row tiles (kernel 5; force_stages 203 forces them): loop trips of both K-groups over the
  * workgroup's K-tile slice [kt0, kt1), and the K-tile group g (0 | 1) takes on a trip (a tile >= kt1: no MFMAs). */
 int tair_k_kgroup_trips(int kt0, int kt1);

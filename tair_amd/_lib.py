@@ -117,6 +117,29 @@ class GemmDesc(ctypes.Structure):
     ]
 
 
+class AttnLane(ctypes.Structure):
+    """tair_attn_lane: one lane of tair_k_attention_grouped."""
+    _fields_ = [("q", ctypes.c_void_p), ("ldq", ctypes.c_int), ("k", ctypes.c_void_p), ("ldk", ctypes.c_int),
+                ("v", ctypes.c_void_p), ("ldv", ctypes.c_int), ("o", ctypes.c_void_p), ("ldo", ctypes.c_int),
+                ("kv_bstride", ctypes.c_int), ("ws", ctypes.c_void_p), ("ws_bytes", ctypes.c_int64),
+                ("tickets", ctypes.c_void_p), ("tickets_cap", ctypes.c_int)]
+
+
+class LnLane(ctypes.Structure):
+    """tair_ln_lane: one lane of tair_k_layernorm_grouped."""
+    _fields_ = [("x", ctypes.c_void_p), ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p), ("y", ctypes.c_void_p),
+                ("y8", ctypes.c_void_p), ("s8", ctypes.c_void_p), ("ld8", ctypes.c_int)]
+
+
+class GnLane(ctypes.Structure):
+    """tair_gn_lane: one lane of tair_k_groupnorm_grouped / tair_k_gn_apply_stats_grouped."""
+    _fields_ = [("x", ctypes.c_void_p), ("ldx", ctypes.c_int), ("gamma", ctypes.c_void_p), ("beta", ctypes.c_void_p),
+                ("ss", ctypes.c_void_p), ("ws", ctypes.c_void_p), ("tickets", ctypes.c_void_p),
+                ("y", ctypes.c_void_p), ("ldy", ctypes.c_int), ("st", ctypes.c_void_p), ("st_rs", ctypes.c_int),
+                ("x_lo", ctypes.c_int), ("y_split", ctypes.c_int), ("y8", ctypes.c_void_p), ("ld8", ctypes.c_int),
+                ("inv8", ctypes.c_void_p)]
+
+
 # every symbol include/tair_cldm.h and include/tair_kernels.h declare, with its ctypes signature
 _P = ctypes.c_void_p
 _I = ctypes.c_int
@@ -151,6 +174,14 @@ SIGNATURES = {
     "tair_fault_count": (_I, [_I, ctypes.POINTER(_I)]),
     "tair_k_gemm_plan": (_I, [ctypes.POINTER(GemmDesc), ctypes.POINTER(_I), ctypes.POINTER(_I), ctypes.POINTER(_I),
                               ctypes.POINTER(_I)]),
+    "tair_k_gemm_grouped": (_I, [ctypes.POINTER(GemmDesc), _I, _P]),
+    "tair_k_gemm_plan_lanes": (_I, [ctypes.POINTER(GemmDesc), _I, ctypes.POINTER(_I), ctypes.POINTER(_I),
+                                    ctypes.POINTER(_I), ctypes.POINTER(_I)]),
+    "tair_k_gemm_grouped_check": (_I, [ctypes.POINTER(GemmDesc), _I]),
+    "tair_k_attention_grouped": (_I, [ctypes.POINTER(AttnLane), _I, _I, _I, _I, _I, ctypes.c_float, _I, _I, _P]),
+    "tair_k_layernorm_grouped": (_I, [ctypes.POINTER(LnLane), _I, _I, _I, ctypes.c_float, _P]),
+    "tair_k_groupnorm_grouped": (_I, [ctypes.POINTER(GnLane), _I, _I, _I, _I, _I, ctypes.c_float, _I, _P]),
+    "tair_k_gn_apply_stats_grouped": (_I, [ctypes.POINTER(GnLane), _I, _I, _I, _I, _I, ctypes.c_float, _I, _P]),
     "tair_k_kgroup_trips": (_I, [_I, _I]),
     "tair_k_gemm_kgroup_force": (_I, [_I]),
     "tair_k_kgroup_tile": (_I, [_I, _I, _I]),

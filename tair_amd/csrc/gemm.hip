@@ -514,6 +514,13 @@ hipError_t gemm_plan_query(const GemmArgs& a, int* bm, int* bn, int* splits, int
   return e;
 }
 
+hipError_t gemm_grouped_check(const GemmArgs* a, int n) {
+  g_gemm_dry = true;
+  const hipError_t e = gemm_grouped(a, n, nullptr);
+  g_gemm_dry = false;
+  return e;
+}
+
 hipError_t gemm_grouped(const GemmArgs* args, int n, hipStream_t s) {
   if (!g_gemm_dry) TAIR_HIP_CHECK(gemm_init());  // (a dry planning run touches no device: CPU-testable)
   if (n < 1 || n > MAX_GROUP) {
@@ -524,7 +531,8 @@ hipError_t gemm_grouped(const GemmArgs* args, int n, hipStream_t s) {
   for (int i = 1; i < n; ++i) {
     const GemmArgs& b = args[i];
     if (b.M != a.M || b.N != a.N || b.K != a.K || b.Kx != a.Kx || b.amode != a.amode || b.C != a.C ||
-        b.H != a.H || b.W != a.W || b.Ho != a.Ho || b.Wo != a.Wo || b.act != a.act || b.out_f32 != a.out_f32) {
+        b.H != a.H || b.W != a.W || b.Ho != a.Ho || b.Wo != a.Wo || b.act != a.act || b.out_f32 != a.out_f32 ||
+        b.out_split != a.out_split) {
       set_error("gemm: grouped GEMMs must share shape, mode and epilogue kind");
       return hipErrorInvalidValue;
     }
@@ -538,26 +546,30 @@ hipError_t gemm_grouped(const GemmArgs* args, int n, hipStream_t s) {
     set_error("gemm: act %d (0 none, 1 SiLU, 2 GEGLU, 3 GELU)", a.act);
     return hipErrorInvalidValue;
   }
-  // GELU (nn.GELU of the CLIP text tower's MLP, transformer.py:199-256): the dense bf16 linears only
-  if (a.act == 3 && (a.amode != A_DENSE || a.f8 || a.out_split || a.st[0].acc || a.rst || a.gn_st)) {
-    set_error("gemm: the GELU epilogue takes a dense bf16 GEMM without split planes or statistics targets");
-    return hipErrorInvalidValue;
-  }
-  if (a.out_split && (a.act == 2 || a.out_f32 || a.ldo < 3 * a.N)) {
-    set_error("gemm: split output needs a plain epilogue and ldo >= 3N (N=%d, ldo=%d)", a.N, a.ldo);
-    return hipErrorInvalidValue;
-  }
-  if (a.act == 2 && (a.N % 4 || a.out_f32)) {
-    set_error("gemm: GEGLU epilogue needs N %% 4 == 0 and bf16 output (N=%d)", a.N);
-    return hipErrorInvalidValue;
-  }
-  if (a.out_lo && (a.out_f32 || a.out_split || a.act == 2)) {
-    set_error("gemm: two-plane (out_lo) output needs a plain bf16 epilogue");
-    return hipErrorInvalidValue;
-  }
-  if (a.x_wrap && (a.Kx != 2 * a.x_wrap || a.x_wrap % kq)) {
-    set_error("gemm: x_wrap %d needs Kx = 2 * x_wrap (Kx %d)", a.x_wrap, a.Kx);
-    return hipErrorInvalidValue;
+  // per-descriptor rules: every lane of the group (a lane's ldo, out_lo, x_wrap and targets are its own)
+  for (int i = 0; i < n; ++i) {
+    const GemmArgs& a = args[i];
+    // GELU (nn.GELU of the CLIP text tower's MLP, transformer.py:199-256): the dense bf16 linears only
+    if (a.act == 3 && (a.amode != A_DENSE || a.f8 || a.out_split || a.st[0].acc || a.rst || a.gn_st)) {
+      set_error("gemm: the GELU epilogue takes a dense bf16 GEMM without split planes or statistics targets");
+      return hipErrorInvalidValue;
+    }
+    if (a.out_split && (a.act == 2 || a.out_f32 || a.ldo < 3 * a.N)) {
+      set_error("gemm: split output needs a plain epilogue and ldo >= 3N (N=%d, ldo=%d)", a.N, a.ldo);
+      return hipErrorInvalidValue;
+    }
+    if (a.act == 2 && (a.N % 4 || a.out_f32)) {
+      set_error("gemm: GEGLU epilogue needs N %% 4 == 0 and bf16 output (N=%d)", a.N);
+      return hipErrorInvalidValue;
+    }
+    if (a.out_lo && (a.out_f32 || a.out_split || a.act == 2)) {
+      set_error("gemm: two-plane (out_lo) output needs a plain bf16 epilogue");
+      return hipErrorInvalidValue;
+    }
+    if (a.x_wrap && (a.Kx != 2 * a.x_wrap || a.x_wrap % kq)) {
+      set_error("gemm: x_wrap %d needs Kx = 2 * x_wrap (Kx %d)", a.x_wrap, a.Kx);
+      return hipErrorInvalidValue;
+    }
   }
   if (a.Kx % kq) {
     set_error("gemm: Kx=%d not a multiple of %d", a.Kx, kq);
@@ -579,14 +591,17 @@ hipError_t gemm_grouped(const GemmArgs* args, int n, hipStream_t s) {
       set_error("gemm: grouped GEMMs must share the operand type");
       return hipErrorInvalidValue;
     }
-  if (a.rst && (a.out_f32 || a.out_split || a.act == 2 || a.st[0].acc || (a.probe & ~128))) {
-    set_error("gemm: LayerNorm row statistics need a plain bf16 epilogue without GroupNorm targets");
-    return hipErrorInvalidValue;
-  }
-  if (a.lnst && (!a.lncs || a.amode != A_DENSE || a.Kx || a.f8 || !(a.ln_c > 0.f) || a.rst || a.st[0].acc ||
-                 (a.N & 7))) {
-    set_error("gemm: a folded LayerNorm takes a dense bf16 GEMM with column sums and 1/C");
-    return hipErrorInvalidValue;
+  for (int i = 0; i < n; ++i) {
+    const GemmArgs& a = args[i];
+    if (a.rst && (a.out_f32 || a.out_split || a.act == 2 || a.st[0].acc || (a.probe & ~128))) {
+      set_error("gemm: LayerNorm row statistics need a plain bf16 epilogue without GroupNorm targets");
+      return hipErrorInvalidValue;
+    }
+    if (a.lnst && (!a.lncs || a.amode != A_DENSE || a.Kx || a.f8 || !(a.ln_c > 0.f) || a.rst || a.st[0].acc ||
+                   (a.N & 7))) {
+      set_error("gemm: a folded LayerNorm takes a dense bf16 GEMM with column sums and 1/C");
+      return hipErrorInvalidValue;
+    }
   }
   for (int i = 1; i < n; ++i)
     if ((args[i].rst != nullptr) != (a.rst != nullptr) || (args[i].lnst != nullptr) != (a.lnst != nullptr)) {
@@ -684,7 +699,9 @@ hipError_t gemm_grouped(const GemmArgs* args, int n, hipStream_t s) {
   // GroupNorm on load: the software-pipelined tile kernels (<= 128-row tiles, or 256 x 128) and the halo
   // tiles, a tile inside one batch element, bf16 conv (stride 1) or dense operands
   for (int i = 1; i < n; ++i)
-    if ((args[i].gn_st != nullptr) != (a.gn_st != nullptr)) {
+    if ((args[i].gn_st != nullptr) != (a.gn_st != nullptr) ||
+        (a.gn_st && (!args[i].gn_gamma || !args[i].gn_beta || args[i].gn_G != a.gn_G ||
+                     args[i].rows_per_b != a.rows_per_b))) {  // (the table's LDS is sized from lane 0)
       set_error("gemm: grouped GEMMs must share the GroupNorm-on-load role");
       return hipErrorInvalidValue;
     }

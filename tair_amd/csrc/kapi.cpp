@@ -75,6 +75,86 @@ int tair_k_gemm_plan(const tair_gemm_desc* d, int* bm, int* bn, int* splits, int
   return gemm_plan_query(a, bm, bn, splits, kern) == hipSuccess ? 0 : -2;
 }
 
+namespace {
+// the lanes of a grouped test entry: at most MAX_GROUP are converted; a count outside 1..MAX_GROUP goes to the
+// launcher as it is, which refuses it before any launch
+int lanes_of(int n) { return n < 0 ? 0 : n > MAX_GROUP ? MAX_GROUP : n; }
+GnArgs gn_args_of(const tair_gn_lane& l, float eps) {
+  GnArgs g{};
+  g.x = (const bf16*)l.x; g.ldx = l.ldx; g.gamma = l.gamma; g.beta = l.beta; g.ss = l.ss; g.ws = l.ws;
+  g.tickets = l.tickets; g.y = (bf16*)l.y; g.ldy = l.ldy; g.st = l.st; g.st_rs = l.st_rs; g.eps = eps;
+  g.x_lo = l.x_lo; g.y_split = l.y_split; g.y8 = (uint8_t*)l.y8; g.ld8 = l.ld8; g.inv8 = l.inv8;
+  return g;
+}
+}  // namespace
+
+int tair_k_gemm_grouped(const tair_gemm_desc* d, int n, void* stream) {
+  if (!d) return -1;
+  GemmArgs a[MAX_GROUP] = {};
+  for (int i = 0; i < lanes_of(n); ++i) a[i] = gemm_args_of(d + i);
+  return gemm_grouped(a, n, (hipStream_t)stream) == hipSuccess ? 0 : -2;
+}
+
+int tair_k_gemm_plan_lanes(const tair_gemm_desc* d, int lanes, int* bm, int* bn, int* splits, int* kern) {
+  if (!d || !bm || !bn || !splits || !kern || lanes < 1 || lanes > MAX_GROUP) return -1;
+  const GemmArgs a = gemm_args_of(d);
+  return gemm_plan_query(a, bm, bn, splits, kern, lanes) == hipSuccess ? 0 : -2;
+}
+
+int tair_k_gemm_grouped_check(const tair_gemm_desc* d, int n) {
+  if (!d) return -1;
+  GemmArgs a[MAX_GROUP] = {};
+  for (int i = 0; i < lanes_of(n); ++i) a[i] = gemm_args_of(d + i);
+  return gemm_grouped_check(a, n) == hipSuccess ? 0 : -2;
+}
+
+int tair_k_attention_grouped(const tair_attn_lane* l, int n, int B, int H, int Sq, int Skv, float scale,
+                             int force_qsets, int force_splits, void* stream) {
+  if (!l) return -1;
+  AttnArgs a[MAX_GROUP] = {};
+  for (int i = 0; i < lanes_of(n); ++i)
+    a[i] = AttnArgs{(const bf16*)l[i].q, l[i].ldq, (const bf16*)l[i].k, l[i].ldk, (const bf16*)l[i].v, l[i].ldv,
+                    (bf16*)l[i].o, l[i].ldo, l[i].kv_bstride, l[i].ws, l[i].ws ? (size_t)l[i].ws_bytes : 0,
+                    l[i].tickets, l[i].tickets_cap};
+  return attention_grouped(a, n, B, H, Sq, Skv, scale, (hipStream_t)stream, force_qsets, force_splits) == hipSuccess
+             ? 0 : -2;
+}
+
+int tair_k_layernorm_grouped(const tair_ln_lane* l, int n, int T, int C, float eps, void* stream) {
+  if (!l) return -1;
+  LnArgs a[MAX_GROUP] = {};
+  for (int i = 0; i < lanes_of(n); ++i)
+    a[i] = LnArgs{(const bf16*)l[i].x, l[i].gamma, l[i].beta, (bf16*)l[i].y, (uint8_t*)l[i].y8, l[i].s8, l[i].ld8};
+  return layernorm_grouped(a, n, T, C, eps, (hipStream_t)stream) == hipSuccess ? 0 : -2;
+}
+
+int tair_k_groupnorm_grouped(const tair_gn_lane* l, int n, int B, int HW, int C, int G, float eps, int silu,
+                             void* stream) {
+  if (!l) return -1;
+  GnArgs a[MAX_GROUP] = {};
+  for (int i = 0; i < lanes_of(n); ++i) {
+    a[i] = gn_args_of(l[i], eps);
+    a[i].st = nullptr;  // (this entry applies from the scale / shift it has just made)
+  }
+  hipStream_t s = (hipStream_t)stream;
+  if (groupnorm_stats_grouped(a, n, B, HW, C, G, eps, s) != hipSuccess) return -2;
+  return groupnorm_apply_grouped(a, n, B, HW, C, silu, s, G) == hipSuccess ? 0 : -2;
+}
+
+int tair_k_gn_apply_stats_grouped(const tair_gn_lane* l, int n, int B, int HW, int C, int G, float eps, int silu,
+                                  void* stream) {
+  if (!l) return -1;
+  GnArgs a[MAX_GROUP] = {};
+  for (int i = 0; i < lanes_of(n); ++i) a[i] = gn_args_of(l[i], eps);
+  if (n >= 1 && n <= MAX_GROUP)
+    for (int i = 0; i < n; ++i)
+      if (!a[i].st) {
+        set_error("gn_apply_stats_grouped: lane %d without producer statistics", i);
+        return -1;
+      }
+  return groupnorm_apply_grouped(a, n, B, HW, C, silu, (hipStream_t)stream, G) == hipSuccess ? 0 : -2;
+}
+
 int tair_k_gemm_kgroup_force(int on) { return (int)gemm_set_kgroup_force(on != 0); }
 int tair_k_kgroup_trips(int kt0, int kt1) { return kgroup_trips(kt0, kt1); }
 int tair_k_kgroup_tile(int kt0, int g, int trip) { return kgroup_tile(kt0, g, trip); }

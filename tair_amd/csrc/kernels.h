@@ -166,6 +166,8 @@ hipError_t gemm_grouped(const GemmArgs* a, int n, hipStream_t s);  // n <= MAX_G
 bool gemm_gn_ok(const GemmArgs& a);  // a GroupNorm-on-load plan exists for a (validation only, no launch)
 // the plan gemm_grouped would launch for a (validation only, touches no device)
 hipError_t gemm_plan_query(const GemmArgs& a, int* bm, int* bn, int* splits, int* kern, int lanes = 1);
+// gemm_grouped's validation and planning for n descriptors of their own (touches no device, launches nothing)
+hipError_t gemm_grouped_check(const GemmArgs* a, int n);
 hipError_t gemm_init();  // one-time kernel attribute setup (call outside stream capture)
 // Faults the GEMM kernels detected since the last call (a cooperative split-K slice that gave up waiting for
 // its tile's other slices and therefore summed incomplete slabs); reset = true clears the counter.  Host

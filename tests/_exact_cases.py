@@ -112,10 +112,11 @@ def src_k(src) -> Tuple[int, int, int]:
 
 
 class Case:
-    def __init__(self, name, src, N, epi, force, expect, combine=None, refusal=None):
+    def __init__(self, name, src, N, epi, force, expect, combine=None, refusal=None, lane=0):
         self.name, self.src, self.N, self.epi, self.force = name, src, N, epi, force
         self.expect = tuple(expect) if expect is not None else None
         self.combine, self.refusal = combine, refusal
+        self.lane = lane  # the operand set's lane salt (a GroupCase's second lane: 1)
 
     @property
     def is_conv(self):
@@ -438,14 +439,17 @@ def int_matmul(a: torch.Tensor, w: torch.Tensor) -> torch.Tensor:
 
 class Ops:
     """Integer operands of (source, N, feature set) on the CPU and the int64 reference of TWICE the epilogue's value
-    (alpha = 0.5 gives half-integers), on `dev`."""
+    (alpha = 0.5 gives half-integers), on `dev`.  `lane` salts the seed: lane 0 draws the operands every single-lane
+    case has always had, lane 1 an independent set under the same rule (the second lane of a grouped launch), with
+    the time-embedding rows in the other order."""
 
-    def __init__(self, src, N, epi):
-        self.src, self.N, self.epi = src, N, epi
+    def __init__(self, src, N, epi, lane=0):
+        self.src, self.N, self.epi, self.lane = src, N, epi, lane
         self.f = f = EPI[epi]
         self.B, self.hw, self.M = src_shape(src)
         self.Kd, self.Kreal, self.Kx = src_k(src)
-        gen = torch.Generator().manual_seed(zlib.crc32(repr((src, N, epi)).encode()))
+        key = (src, N, epi) if lane == 0 else (src, N, epi, lane)
+        gen = torch.Generator().manual_seed(zlib.crc32(repr(key).encode()))
         B, M = self.B, self.M
         if src[0] == "dense":
             _, self.amode, _, _, _, self.x_wrap, self.f8 = src
@@ -472,7 +476,7 @@ class Ops:
         self.emb = self.emb_row = self.res = None
         if f.get("emb"):  # B + 1 rows, batch element b reads row B - b: row 0 is never read
             self.emb = torch.randint(-SMALL, SMALL + 1, (B + 1, N), generator=gen)
-            self.emb_row = torch.tensor([B - b for b in range(B)], dtype=torch.int32)
+            self.emb_row = torch.tensor([B - b if lane == 0 else b + 1 for b in range(B)], dtype=torch.int32)
         if f.get("res"):
             self.res = torch.randint(-SMALL, SMALL + 1, (M, N), generator=gen)
         self.half = bool(f.get("half"))
@@ -559,7 +563,7 @@ _OPS: Dict[tuple, Ops] = {}
 
 
 def operands(case: Case) -> Ops:
-    key = (case.src, case.N, case.epi)
+    key = (case.src, case.N, case.epi, case.lane)
     if key not in _OPS:
         _OPS[key] = Ops(*key)
     return _OPS[key]
@@ -658,6 +662,215 @@ AGREE = [
      len(ALL_PLANS) - 8 - 2),
     (Case("agree-conv2x16x16c128n72", conv(A_CONV3, 2, 16, 16, 128), 72, "br", None, None), len(ALL_PLANS) - 2 - 2),
 ]
+
+
+# ---- two lanes in one launch (tair_k_gemm_grouped) ---------------------------------------------------------------------
+class GroupCase:
+    """Two same-shape GEMMs / convs as lanes 0 and 1 of ONE launch (a UNet layer and the same ControlNet layer in the
+    product).  The lanes share the source, N, the forced plan, the combine and the output kind (out_f32, out_split,
+    operand type), as the launcher demands; their feature sets epis[0] | epis[1] may differ -- epilogue_tile picks its
+    features per tile from that tile's lane.  Lane i's operands are Ops(src, N, epis[i], lane=i): an independent draw
+    under the same rule.  expect is the plan of TWO lanes (tair_k_gemm_plan_lanes); expect_one, where given, the plan
+    the same request gets alone (the planner's own plans that differ)."""
+
+    def __init__(self, name, src, N, epis, force, expect, combine=None, expect_one=None, tags=()):
+        self.name, self.src, self.N, self.epis, self.force = name, src, N, tuple(epis), force
+        self.expect, self.combine, self.expect_one, self.tags = tuple(expect), combine, expect_one, frozenset(tags)
+
+    @property
+    def is_conv(self):
+        return self.src[0] == "conv"
+
+    def lane(self, i) -> Case:
+        return Case(f"{self.name}[lane {i}]", self.src, self.N, self.epis[i], self.force, self.expect, self.combine,
+                    lane=i)
+
+    def workgroups(self) -> int:
+        """tiles_m * 2 * tiles_n * splits of the main kernel's grid."""
+        _, bm, bn, splits = self.expect
+        return cdiv(src_shape(self.src)[2], abs(bm)) * 2 * cdiv(self.N, bn) * splits
+
+    def __repr__(self):
+        return self.name
+
+
+def src_name(src) -> str:
+    if src[0] == "dense":
+        _, _, M, K, Kx, xw, f8 = src
+        return ("f8" if f8 else "") + f"dense-m{M}k{K}" + (f"x{Kx}" if Kx else "") + ("w" if xw else "")
+    _, amode, B, H, W, C, Kx, xw, f8, sh = src
+    kind = {A_CONV3: "conv", A_CONV3_S2: "s2conv", A_CONV3_UP: "upconv", A_SMALLC: "smallc"}[amode]
+    return ("f8" if f8 else "") + f"{kind}{B}x{H}x{W}c{C}" + (f"x{Kx}" if Kx else "") + ("w" if xw else "") + \
+        (f"-shift{sh}" if amode == A_CONV3_S2 else "")
+
+
+GROUP_CASES: List[GroupCase] = []
+# mixed pairs both ways round, then pairs of one feature set (whose two lanes still differ in every operand)
+G_MIXED = (("b", "ber"), ("br", "b"), ("lo", "br"), ("half", "b"), ("ber", "b"), ("b", "br"), ("br", "lo"),
+           ("b", "half"))
+G_PAIRS = G_MIXED + (("be", "ber"), ("f32", "half32"), ("sp1", "sp1"), ("sp2", "sp2"), ("half32", "f32"), ("lo", "lo"))
+G_PAIRS_HALO = (("b", "ber"), ("br", "b"), ("lo", "br"), ("ber", "b"), ("f32", "f32"), ("br", "lo"))  # H_EPI's sets
+G_PAIRS_F8 = (("b", "br"), ("lo", "br"), ("f32", "f32"), ("br", "b"))  # F8_EPI's sets
+G_M, G_N = (63, 130, 257), (70, 200)  # tiles_m 1 / 3 / 5 at 64 rows, 1 / 2 / 3 at 128, 1 / 1 / 2 at 256
+
+
+def _gkind(force):
+    if force is None:
+        return "own"
+    bm, bn, _, st = force
+    kind = "kgroup" if st >= 200 else f"deep-s{st - 100}-" if st >= 100 else "halo" if st == 9 else "phase" if st == 4 \
+        else "shallow" if st == 2 else "ring" if bm < 0 else "tile"
+    return f"{kind}{abs(bm)}x{bn}"
+
+
+def _gadd(src, N, pair, force, combine=None, expect=None, expect_one=None, tags=()):
+    if expect is None:
+        expect = expect_forced(src, force)
+    if expect[3] == 1 and force is not None:
+        combine = None
+    name = f"g-{_gkind(force)}-{src_name(src)}-n{N}-s{expect[3]}" + (f"-{combine}" if combine and expect[3] > 1 else "") + \
+        f"-{pair[0]}+{pair[1]}"
+    GROUP_CASES.append(GroupCase(name, src, N, pair, force, expect, combine, expect_one, tags))
+
+
+_G_FAMILIES = [(bm, bn, T3) for bm, bn in ((64, 64), (64, 128), (128, 128), (128, 320), (256, 128), (256, 160))] + \
+              [(-64, 64, 0), (-128, 256, 0), (-256, 128, 0), (64, 64, 104), (64, 64, 108), (64, 64, 203), (64, 128, 203),
+               (256, 256, 4), (256, 320, 4), (64, 64, 2), (64, 128, 2)]
+# -- every family unsplit: dense, (M, N) running through all six combinations, the K-extension and the pairs rotating
+for _i, (_bm, _bn, _st) in enumerate(_G_FAMILIES):
+    _Kx = (0, 64, 0, 128)[_i % 4]
+    _gadd(dense(G_M[_i % 3], 160 if _bm < 0 else 192, _Kx, 64 if _Kx == 128 else 0), G_N[_i % 2], G_PAIRS[_i % len(G_PAIRS)],
+          (_bm, _bn, 1, _st), tags=("family",))
+# -- every family that splits, split: the reduce kernel everywhere, the in-kernel combines on the 64-row tiles
+for _i, (_bm, _bn, _st) in enumerate(_G_FAMILIES):
+    if _st in (4, 2):
+        continue  # (the 4-phase kernel and the 2-stage tiles never split)
+    _modes = ("coop", "last", "reduce") if (abs(_bm) == 64 and _bm > 0 and not 100 <= _st < 200) else \
+        ("last", "reduce") if 100 <= _st < 200 else ("reduce",)
+    for _j, _mode in enumerate(_modes):
+        _src, _N = ((SPLIT_SRC, 200), (SPLIT_SRC_X, 70))[(_i + _j) % 2]
+        _gadd(_src, _N, G_PAIRS[(_i + 3 * _j + 5) % len(G_PAIRS)], (_bm, _bn, 3 if _bm < 0 else 2, _st), _mode,
+              tags=("family",))
+# -- the lane boundary under xcd_remap: tiles_m 1 / 3 / 5 with two and four n-tiles, unsplit and in three slices with
+# the cooperative order (modes 3 / 4): tiles_m * 2 * tiles_n * splits is a multiple of 8 for some and not for others
+for _i, (_M, _N) in enumerate((m, n) for m in G_M for n in G_N):
+    _gadd(dense(_M, 320), _N, G_MIXED[_i % 8], (64, 64, 1, T3), tags=("boundary",))
+    _gadd(dense(_M, 320), _N, G_MIXED[(_i + 3) % 8], (64, 64, 3, T3), "coop", tags=("boundary",))
+    _gadd(dense(_M, 320), _N, G_MIXED[(_i + 5) % 8], (128, 128, 2, T3), "reduce", tags=("boundary",))
+# -- every combine at 2, 3 and 5 slices, dense (five K-tiles) and conv (ten)
+for _i, _s in enumerate((2, 3, 5)):
+    for _j, _mode in enumerate(("coop", "last", "reduce")):
+        _gadd(SPLIT_SRC, 200, G_PAIRS[(3 * _i + _j) % len(G_PAIRS)], (64, 64, _s, T3), _mode, tags=("combine",))
+        _gadd(SPLIT_SRC_X, 70, G_PAIRS[(3 * _i + _j + 4) % len(G_PAIRS)], (64, 128, _s, T3), _mode, tags=("combine",))
+        _gadd(CS_SRC, 72, G_MIXED[(3 * _i + _j) % 8], (64, 64, _s, T3), _mode, tags=("combine",))
+# -- conv sources: stride 1 (C = 64 / 192, with and without the K-extension, x_wrap), stride 2 at both shifts, the
+# fused upsample, the small-channel mode, halo tiles at the three widths, fp8
+for _i, ((_B, _H, _W), _C, (_Kx, _xw)) in enumerate((((3, 5, 7), 64, (0, 0)), ((2, 8, 16), 192, (64, 0)),
+                                                      ((1, 30, 24), 64, (128, 64)), ((3, 5, 7), 192, (64, 0)),
+                                                      ((2, 8, 16), 64, (128, 64)), ((1, 30, 24), 192, (0, 0)))):
+    _force = ((64, 64, 1, T3), (128, 128, 1, T3), (-128, 256, 1, 0), (64, 64, 1, 104), (64, 128, 1, 203),
+              (256, 320, 1, 4))[_i]
+    _gadd(conv(A_CONV3, _B, _H, _W, _C, _Kx, _xw), (72, 200)[_i % 2], G_PAIRS[(2 * _i) % len(G_PAIRS)], _force,
+          tags=("conv1",))
+_gadd(CS_SRC, 72, ("ber", "b"), (128, 128, 3, T3), "reduce", tags=("conv1",))
+_gadd(CS_SRC, 72, ("lo", "br"), (64, 64, 3, 203), "coop", tags=("conv1",))
+for _sh in (0, 1):
+    _gadd(conv(A_CONV3_S2, 2, 8, 16, 64, 0, 0, 0, _sh), 72, G_MIXED[_sh], (64, 64, 1, T3), tags=("s2",))
+    _gadd(conv(A_CONV3_S2, 2, 8, 16, 128, 0, 0, 0, _sh), 200, G_MIXED[2 + _sh], (64, 128, 2, T3), "reduce", tags=("s2",))
+_gadd(conv(A_CONV3_UP, 2, 4, 8, 64), 72, ("b", "ber"), (64, 64, 1, T3), tags=("up",))
+_gadd(conv(A_CONV3_UP, 2, 4, 8, 128), 200, ("br", "b"), (64, 128, 3, T3), "coop", tags=("up",))
+_gadd(conv(A_SMALLC, 2, 8, 16, 8), 72, ("lo", "br"), (64, 64, 1, T3), tags=("smallc",))
+_gadd(conv(A_SMALLC, 3, 5, 7, 8), 64, ("half", "b"), (64, 128, 2, T3), "reduce", tags=("smallc",))  # 72 -> 2 K-tiles
+for _i, (_B, _H, _W) in enumerate(((1, 16, 16), (2, 32, 16), (1, 8, 32), (1, 64, 64))):
+    _bn = HALO_BN[_W][_i % 3]
+    _gadd(conv(A_CONV3, _B, _H, _W, 192), (72, 200, 64, 72)[_i], G_PAIRS_HALO[_i], (256, _bn, 1, 9), tags=("halo",))
+    _gadd(conv(A_CONV3, _B, _H, _W, 192), (200, 72, 72, 64)[_i], G_PAIRS_HALO[(_i + 2) % 6], (256, _bn, (3, 2, 3, 2)[_i], 9),
+          "reduce", tags=("halo",))
+_gadd(dense(65, 128, 0, 0, 1), 70, G_PAIRS_F8[0], (64, 64, 1, 0), tags=("f8",))
+_gadd(dense(257, 640, 0, 0, 1), 200, G_PAIRS_F8[1], (64, 64, 2, 0), "last", tags=("f8",))
+_gadd(dense(257, 384, 0, 0, 1), 200, G_PAIRS_F8[2], (128, 128, 3, 0), "reduce", tags=("f8",))
+_gadd(conv(A_CONV3, 2, 8, 16, 64, 0, 0, 1), 70, G_PAIRS_F8[3], (64, 64, 1, 0), tags=("f8",))
+_gadd(conv(A_CONV3, 3, 5, 7, 128, 64, 0, 1), 200, G_PAIRS_F8[0], (128, 128, 2, 0), "reduce", tags=("f8",))
+# -- the planner's own plans where two lanes plan differently from one (gemm_plan / kgroup_rule, by hand)
+# dense 257 x 200 x 320 with a K-extension of 64 (the composite FF-out rule): 5 x 4 = 20 tiles of 64 x 64, 6 K-tiles.
+#   One lane: no slice count c with 6 / c >= 10: unsplit.  Two lanes: (200 + 10) / 20 = 10 slices, capped at
+#   2 * 6 / 5 = 2; a dense GEMM never takes the two-K-group form by rule
+_gadd(dense(257, 320, 64), 200, ("lo", "br"), None, "coop", (K_TILE, 64, 64, 2), (K_TILE, 64, 64, 1), tags=("own",))
+# conv 1 x 30 x 24, C = 64 -> N = 72: BNc = 64, 12 x 2 = 24 tiles, (400 + 12) / 24 = 17 slices capped at 9 / 3 = 3.
+#   One lane: 24 < 32 tiles, no two-K-group plan (kgroup_rule).  Two lanes: 48 tiles in [32, 256], 48 * 3 <= 512,
+#   one image, tickets: min(256 / 48, 9 / 15) = 0 -> one slice of 9 >= 4 K-tiles: the two-K-group kernel, unsplit
+_gadd(conv(A_CONV3, 1, 30, 24, 64), 72, ("be", "ber"), None, "coop", (K_KGROUP, 64, 64, 1), (K_TILE, 64, 64, 3),
+      tags=("own",))
+# -- the blocked workgroup order (xcd_remap mode 5) with two lanes.  The host rule (gemm.hip): dense, one slice, a
+# 3-stage tile; with gx = 2 * tiles_m and gy = tiles_n: gx * gy > 512, weights gy * bn * K * 2 bytes > 2 MiB, and a block
+# of bmr x bnc tiles (bmr | gx, bnc | gy, 16 <= bmr * bnc <= 64, (gx / bmr) * (gy / bnc) % 8 == 0) whose traffic
+# ab * gy / bnc + wb * gx / bmr is below 0.7 x the better of the two plain orders (blocked_pick below is that rule).
+# On the smallest tile, 64 x 64, with M = 130 (tiles_m = 3: gx = 6, so a block of bmr = 2 rows holds the last m-tile of
+# lane 0 and the first of lane 1), N = 6 (mod 64) as the other cases and K a multiple of 64 with more than one K-tile:
+# gy >= 86 for the grid, and the weights need gy * 64 * K > 2^20; the smallest weight matrix that also has an admissible
+# block is K = 192, gy = 88 (N = 5574, block 2 x 11: 3 x 8 = 24 blocks); gy = 86, 87 have no divisor pair that
+# passes.  One lane of the same shape has gx * gy = 264 <= 512 and keeps the plain order.
+BLOCKED = (130, 5574, 192)
+_gadd(dense(BLOCKED[0], BLOCKED[2]), BLOCKED[1], ("b", "br"), (64, 64, 1, T3), tags=("blocked",))
+
+GROUP_CASE = {c.name: c for c in GROUP_CASES}
+assert len(GROUP_CASE) == len(GROUP_CASES), [c.name for c in GROUP_CASES if sum(d.name == c.name for d in GROUP_CASES) > 1]
+
+
+def blocked_pick(M, N, K, bm, bn, lanes) -> Tuple[int, int]:
+    """(bmr, bnc) of the blocked order gemm_grouped picks for a dense one-slice bm x bn tile plan of `lanes` lanes, or
+    (0, 0): the rule of gemm.hip, re-stated."""
+    gx, gy = cdiv(M, bm) * lanes, cdiv(N, bn)
+    wb, ab = bn * K * 2.0 * gy, M * K * 2.0 * lanes
+    if not (gx * gy > 512 and wb > (2 << 20)):
+        return 0, 0
+    best, pick = min(ab + wb * gx, ab * gy + wb), (0, 0)
+    for bnc in range(1, 17):
+        for bmr in range(1, 17):
+            if gy % bnc or gx % bmr or not 16 <= bmr * bnc <= 64 or ((gx // bmr) * (gy // bnc)) % 8:
+                continue
+            c = ab * (gy // bnc) + wb * (gx // bmr)
+            if c < 0.7 * best:
+                best, pick = c, (bmr, bnc)
+    return pick
+
+
+def pair_descs(gc: GroupCase, ptrs=None):
+    """The two descriptors of a pair as one ctypes array (what tair_k_gemm_grouped takes).  ptrs: per lane the
+    descriptor fields of its device buffers (tests/test_grouped_exact_gpu.py); None: placeholder pointers, which is
+    all the plan query and the dry check read."""
+    from tair_amd import _lib
+    arr = (_lib.GemmDesc * 2)()
+    for i in range(2):
+        d = planning_desc(gc.lane(i)) if ptrs is None else make_desc(**ptrs[i])
+        ctypes.memmove(ctypes.byref(arr[i]), ctypes.byref(d), ctypes.sizeof(_lib.GemmDesc))
+    return arr
+
+
+def plan_of_lanes(d, lanes) -> Tuple[int, Tuple[int, int, int, int]]:
+    """(status, (kernel, bm, bn, splits)) of tair_k_gemm_plan_lanes: host only."""
+    from tair_amd import _lib
+    out = [ctypes.c_int() for _ in range(4)]
+    rc = _lib.lib().tair_k_gemm_plan_lanes(ctypes.byref(d), lanes, *[ctypes.byref(x) for x in out])
+    bm, bn, splits, kern = (x.value for x in out)
+    return rc, (kern, bm, bn, splits)
+
+
+def swapped_ref2(o: Ops, other: Ops, what: str) -> Optional[torch.Tensor]:
+    """o's reference with ONE per-lane operand taken from the other lane (what a single mixed-up pointer computes), or
+    None where either lane has no such operand.  what: a, w, x, bias, emb, emb_row, res, col_scale, row_scale."""
+    import copy
+    fields = {"a": ("a", "a_col"), "w": ("w_main", "w_x"), "bias": ("bias",)}.get(what, (what,))
+    if any(getattr(o, f) is None or getattr(other, f) is None for f in fields) or (what == "bias" and not o.has_bias):
+        return None
+    m = copy.copy(o)
+    m._ref2 = {}
+    for f in fields:
+        setattr(m, f, getattr(other, f))
+    return m.ref2()
+
+
+SWAPS = ("a", "w", "x", "bias", "emb", "emb_row", "res", "col_scale", "row_scale")
 
 
 # ---- attention ---------------------------------------------------------------------------------------------------------
@@ -779,11 +992,13 @@ def required_targets(Skv, splits, kv_split) -> List[int]:
 class AttnOps:
     """One-hot operands of a case under its effective plan: per (batch, head) the target set (the required keys plus
     random others, at most 64), q / k / v [B, S, H, 64] (float holding bf16 values) and tgt [B, H, Sq], the key each
-    query selects.  A shared context (kv_bstride = 0) has one k / v / target set per head for all batch elements."""
+    query selects.  A shared context (kv_bstride = 0) has one k / v / target set per head for all batch elements.
+    `lane` salts the seed (lane 0: the operands every single-lane case has always had): the second lane of a grouped
+    launch gets target sets, Hadamard rows and V of its own."""
 
-    def __init__(self, c: AttnCase):
+    def __init__(self, c: AttnCase, lane=0):
         B, H, Sq, Skv = c.B, c.H, c.Sq, c.Skv
-        gen = torch.Generator().manual_seed(zlib.crc32(c.name.encode()))
+        gen = torch.Generator().manual_seed(zlib.crc32((c.name if lane == 0 else f"{c.name}#lane{lane}").encode()))
         had = hadamard64()
         req = required_targets(Skv, c.expect[1], c.expect[2])
         assert len(req) <= 64
@@ -814,3 +1029,20 @@ class AttnOps:
             for h in range(H):
                 out[b, :, h] = self.v[b if self.Bk > 1 else 0, self.tgt[b, h], h]
         return out
+
+
+# ---- two attention lanes in one launch (tair_k_attention_grouped) ------------------------------------------------------
+# mode: unsplit; split (no tickets: attn_combine_kernel, lane = blockIdx.y); tk (tickets: merged in-kernel, lane from
+# blockIdx.z / nsplit).  Every lane has its own workspace and tickets (tests/test_grouped_kernels_gpu.py).
+G_ATTN_SQ, G_ATTN_SKV, G_ATTN_BH = (17, 65, 129), (77, 130, 257), ((1, 2), (3, 1), (2, 2))
+GROUP_ATTN_CASES: List[AttnCase] = []
+for _i, _Sq in enumerate(G_ATTN_SQ):
+    for _j, _Skv in enumerate(G_ATTN_SKV):
+        for _m, _mode in enumerate(("unsplit", "split", "tk")):
+            _B, _H = G_ATTN_BH[(_i + _j + _m) % 3]
+            _layout = "shared" if (_i + _j + _m) % 2 and _B > 1 else "rows"
+            _force = ((1, 2)[(_i + _j) % 2], 1 if _mode == "unsplit" else (2, 3, 5)[(_i + _m) % 3])
+            GROUP_ATTN_CASES.append(AttnCase(f"gattn-b{_B}h{_H}q{_Sq}k{_Skv}-{_layout}-q{_force[0]}-{_mode}{_force[1]}", _B, _H,
+                                             _Sq, _Skv, _mode, _force, WS_BIG, attn_expect(_B, _H, _Sq, _Skv, _force, WS_BIG),
+                                             _layout))
+assert len({c.name for c in GROUP_ATTN_CASES}) == len(GROUP_ATTN_CASES)
